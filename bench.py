@@ -8,7 +8,16 @@ resident in HBM.  N GPUs = N ranks (one process per GPU, torch.distributed over 
 sharded, bucketed gradient all-reduce overlapped with backward; value = frames of all ranks /
 max-over-ranks time.  Rank 0 prints one JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp16|bf16|fp32] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp16|bf16|fp32] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (``metric``, ``value``, ``unit``,
+``ms_per_step``, ...; the ``roofline`` block comes from HIP events recorded inside the timed steps and
+costs no run of its own).  ``--full`` adds the measurements that take runs of their own after the
+timed region: the per-site sweep of the 1x1-conv GEMMs (``pointwise``), the CPU baseline
+(``cpu_baseline``) and, with N > 1, the comm-off timing pass (``dp.allreduce_exposed_ms``); without
+it those fields are null.  ``--dump-outputs DIR`` writes what the last timed step returned and left
+behind (``loss``, ``logits``, ``params``, ``buffers``) as ``DIR/<name>.npy``, float32; the inputs
+and initial weights are seeded, so two builds can be compared output for output.
 
 ``--gpus N`` without a launcher: this process spawns ``torch.distributed.run`` with N ranks on
 127.0.0.1 BEFORE touching the GPU and exits with its status (the driver's own
@@ -46,11 +55,19 @@ def parse():
     ap.add_argument("--dtype", default="fp16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--input", default="uint8", choices=["uint8", "fp32"],
                     help="frames handed to the model: raw uint8 crops (normalised in the stem) or fp32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured outside the timed steps: the pointwise sweep and the CPU "
+                         "baseline (N = 1), the comm-off timing pass (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's loss, logits, parameters and buffers to DIR/<name>.npy "
+                         "(git ignores bench_outputs/)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-pw-sweep", action="store_true",
-                    help="skip the per-site timing of the 1x1-conv GEMMs (MFMA utilisation block, N = 1)")
+                    help="with --full: skip the per-site timing of the 1x1-conv GEMMs (MFMA utilisation block, "
+                         "N = 1)")
     ap.add_argument("--cpu-steps", type=int, default=10, help="CPU baseline: timed steps of 32 frames, all threads")
-    ap.add_argument("--no-dp-exposure", action="store_true", help="skip the comm-off timing pass (N > 1)")
+    ap.add_argument("--no-dp-exposure", action="store_true",
+                    help="with --full: skip the comm-off timing pass (N > 1)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend of the N-rank path (nccl = RCCL over xGMI; gloo only for the "
                          "1-GPU rehearsal with DFD_BENCH_DEVICE=0)")
@@ -59,7 +76,10 @@ def parse():
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="kernel-selection knob of the model's plans for A/B runs (dfd_b0_plan_set_tuning), "
                          "e.g. pwl_fused=0")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(n: int) -> int:
@@ -112,6 +132,26 @@ def synthetic_batch(rank: int, device, fmt="uint8"):
     g.manual_seed(1 + 1000 * rank)
     labels = torch.randint(0, 2, (CLIPS,), generator=g, device=device)
     return x, labels
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, tensors: dict):
+    """Write each tensor as out_dir/<name>.npy in float32.  Arrays that would take the dump past
+    DUMP_LIMIT_BYTES are cut to a fixed sample (flattened, indices from numpy's default_rng(0))."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().to("cpu", dtype=torch.float32).numpy() for k, v in tensors.items()}
+    budget = DUMP_LIMIT_BYTES // 4 - 1024 * len(arrays)  # elements; headroom for the .npy headers
+    share = budget // max(1, len(arrays))
+    for name, a in arrays.items():
+        if a.size > share and sum(b.size for b in arrays.values()) > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _cpu_model():
@@ -237,6 +277,8 @@ def main():
     # kernel in the rocprof trace)
     probe = roofline.KernelProbe(model, "dw_bwd", stage=1, block=0)
 
+    last = [None, None]  # (loss, logits) returned by the last timed step
+
     def timed(n, arm=False):
         torch.cuda.synchronize()
         if world > 1:
@@ -246,7 +288,7 @@ def main():
             probe.arm(n)
         t0 = time.perf_counter()
         for _ in range(n):
-            step(x, labels)
+            last[:] = step(x, labels)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         if world > 1:
@@ -261,6 +303,9 @@ def main():
     for _ in range(args.warmup):
         step(x, labels)
     elapsed = timed(args.steps, arm=True)
+    if args.dump_outputs and rank == 0:  # before anything else runs the model or moves its state
+        dump_outputs(args.dump_outputs, {"loss": last[0], "logits": last[1], "params": model._flat_p,
+                                         "buffers": model._flat_b})
     loss, _ = step.forward_backward(x, labels)
     finite = bool(torch.isfinite(loss).item())
     # fp16: the dynamic loss scale after the warmup + timed steps, and how many of them were applied
@@ -274,7 +319,7 @@ def main():
     if world > 1:
         nb = len(step.bucket_log)
         local_el = None
-        if not args.no_dp_exposure:
+        if args.full and not args.no_dp_exposure:
             step.comm_enabled = False  # same step, no all-reduce: what the exchange costs on top
             local_el = timed(args.steps)
             step.comm_enabled = True
@@ -297,11 +342,11 @@ def main():
                           "floor_ms": round(step_bytes / roofline.HBM_PEAK * 1e3, 3),
                           "source": "SURVEY.md §8(d) algorithmic bytes per 256-frame step"}
         pw = None
-        if world == 1 and not args.no_pw_sweep:  # after the timed region; one extra step per site
+        if args.full and world == 1 and not args.no_pw_sweep:  # after the timed region; one extra step per site
             pw = roofline.pointwise_sweep(model, lambda: step(x, labels), H, W, CLIPS * T, es)
             torch.cuda.synchronize()
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_steps)
         line = {
             "metric": METRIC, "value": round(value, 2), "unit": "face-frames/s", "n_gpus": world,

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -25,6 +26,16 @@ def frames(seed, shape):
     mean = torch.tensor([0.485, 0.456, 0.406]).view(1, 1, 3, 1, 1)
     std = torch.tensor([0.229, 0.224, 0.225]).view(1, 1, 3, 1, 1)
     return ((x - mean) / std).float()
+
+
+def load_cnn_lstm_golden(golden_dir):
+    """The CNN-LSTM reference golden as a dict.  Its input ``x`` (2 clips x 16 frames x 3 x 64 x 64,
+    fp32) is stored one clip per file (``cnn_lstm_64.npz``: ``x0``, ``cnn_lstm_64_x1.npz``: ``x1``) so
+    that each fixture stays below 1 MiB."""
+    g = dict(np.load(os.path.join(golden_dir, "cnn_lstm_64.npz")))
+    x1 = np.load(os.path.join(golden_dir, "cnn_lstm_64_x1.npz"))["x1"]
+    g["x"] = np.concatenate([g.pop("x0"), x1])
+    return g
 
 
 def oracle_saved(trunk: torch.nn.Sequential, x: torch.Tensor):

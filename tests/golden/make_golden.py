@@ -215,10 +215,12 @@ def gen_cnn_lstm():
     labels = torch.tensor([1, 0])
     loss = torch.nn.functional.cross_entropy(y, labels)
     loss.backward()
-    rec = dict(x=x.numpy(), y_eval=y_eval.numpy(), y_train=y.detach().numpy(), labels=labels.numpy(),
+    # x one clip per file: each fixture stays below 1 MiB (tests/b0_helpers.py load_cnn_lstm_golden)
+    rec = dict(x0=x.numpy()[:1], y_eval=y_eval.numpy(), y_train=y.detach().numpy(), labels=labels.numpy(),
                loss=np.array(float(loss)), seed=9)
     rec.update(grad_fingerprint(m.named_parameters()))
     np.savez_compressed(os.path.join(HERE, "cnn_lstm_64.npz"), **rec)
+    np.savez_compressed(os.path.join(HERE, "cnn_lstm_64_x1.npz"), x1=x.numpy()[1:])
 
     # collate rules (train.py:38-61) on tiny 4x4 "faces" with M = 0, 5, 16, 23 frames
     batch = []

@@ -23,7 +23,7 @@ from deepfake_amd.weights import deterministic_init_, hash_uniform
 from oracle import b0_cpu
 from oracle.detector_cpu import (CNNLSTMHybridCPU, DetectorCPU, LogicRNNLSTMCPU, collate_cnn_lstm, collate_vit_gcn,
                                  train_step)
-from b0_helpers import frames
+from b0_helpers import frames, load_cnn_lstm_golden
 
 
 def _load(golden_dir, name):
@@ -81,7 +81,20 @@ def test_detector_eval_224_t1_golden(golden_dir):
     assert torch.all(scores == 1.0)  # T = 1: softmax over a single frame
 
 
-def test_detector_train_golden(golden_dir):
+@pytest.fixture
+def golden_threads():
+    """The B0 training goldens hold fp32 gradients of a train-mode BatchNorm stack at 64x64, whose last
+    digits follow the summation order of the CPU kernels, i.e. the number of threads.  They were
+    recorded with 8 threads; compute with 8 whatever the host or OMP_NUM_THREADS offer."""
+    prev = torch.get_num_threads()
+    torch.set_num_threads(8)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(prev)
+
+
+def test_detector_train_golden(golden_dir, golden_threads):
     g = _load(golden_dir, "b0_train_64.npz")
     det = DetectorCPU(dropout_rate=0.0)
     deterministic_init_(det, seed=int(g["seed"]))
@@ -110,7 +123,7 @@ class _EnsembleOfOne(nn.Module):
         return torch.stack([logits]).mean(0), torch.stack([scores]).mean(0)
 
 
-def test_train_step_golden(golden_dir):
+def test_train_step_golden(golden_dir, golden_threads):
     g = _load(golden_dir, "train_step_64.npz")
     ens = _EnsembleOfOne()
     deterministic_init_(ens, seed=int(g["seed"]))
@@ -157,7 +170,7 @@ def test_logic_rnn_sort_quirk():
 
 
 def test_cnn_lstm_golden(golden_dir):
-    g = _load(golden_dir, "cnn_lstm_64.npz")
+    g = load_cnn_lstm_golden(golden_dir)
     m = CNNLSTMHybridCPU(3, 256, 2, 2, 0.0)
     deterministic_init_(m, seed=int(g["seed"]))
     x = torch.from_numpy(g["x"])
