@@ -83,3 +83,299 @@ def rel_err(a: torch.Tensor, b: torch.Tensor) -> float:
     a = a.double()
     b = b.double()
     return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+# ------------------------------------------------------------------ the detector training step
+# One step of the reference recipe (``model(images)`` -> weighted CE -> backward) on the oracle
+# ``DetectorCPU`` and on the HIP detector, at any (clips, frames per clip, H, W).  Every oracle run is
+# cached per shape and never modified by its users.
+
+STEP_SEED = 21
+CLASS_W = torch.tensor([0.7, 1.3])
+_STEP = {}
+
+
+def step_inputs(shape, seed=STEP_SEED):
+    """(frames, labels) of the step at shape = (clips, frames per clip, H, W)"""
+    b, t, h, w = shape
+    x = frames(seed + 1, (b, t, 3, h, w))
+    # channels-last strides, as app.py:2084-2086 / train.py:59 hand the frames over (SURVEY F10)
+    x = x.reshape(b * t, 3, h, w).contiguous(memory_format=torch.channels_last).view(b, t, 3, h, w)
+    labels = torch.tensor([(i * 7 + 1) % 2 for i in range(b)])
+    return x, labels
+
+
+def _oracle_run(shape, mode):
+    from oracle.detector_cpu import DetectorCPU
+    torch.set_num_threads(max(1, min(16, torch.get_num_threads())))
+    x, labels = step_inputs(shape)
+    m = DetectorCPU(dropout_rate=0.0)
+    deterministic_init_(m, seed=STEP_SEED)
+    if mode == "fp64":
+        m = m.double().train()
+        logits, scores = m(x.double())
+        loss = torch.nn.functional.cross_entropy(logits, labels, weight=CLASS_W.double())
+    elif mode == "autocast":
+        m.train()
+        with torch.autocast("cpu", dtype=torch.bfloat16):
+            logits, scores = m(x)
+        loss = torch.nn.functional.cross_entropy(logits.float(), labels, weight=CLASS_W)
+    else:
+        m.train()
+        logits, scores = m(x)
+        loss = torch.nn.functional.cross_entropy(logits, labels, weight=CLASS_W)
+    loss.backward()
+    return dict(logits=logits.detach(), scores=scores.detach(), loss=float(loss.detach()),
+                grads={n: p.grad.detach().clone() for n, p in m.named_parameters()},
+                bufs={n: b.detach().clone() for n, b in m.named_buffers() if "running" in n})
+
+
+def oracle_step(shape):
+    """fp32 CPU oracle: forward, weighted CE, backward (cached per shape)."""
+    key = ("fp32", tuple(shape))
+    if key not in _STEP:
+        _STEP[key] = _oracle_run(shape, "fp32")
+    return _STEP[key]
+
+
+def oracle64_step(shape):
+    """the oracle step in float64 on the CPU (inputs, weights and every op in double; cached):
+    {parameter: gradient}"""
+    key = ("fp64", tuple(shape))
+    if key not in _STEP:
+        _STEP[key] = _oracle_run(shape, "fp64")["grads"]
+    return _STEP[key]
+
+
+def autocast_err(shape):
+    """{tensor: rel. L2 error vs fp64} of torch's CPU bf16 autocast of the oracle step (cached)"""
+    key = ("autocast", tuple(shape))
+    if key not in _STEP:
+        g64 = oracle64_step(shape)
+        ac = _autocast_run(shape)["grads"]
+        _STEP[key] = {n: float((g.double() - g64[n]).norm()) / (float(g64[n].norm()) + 1e-300)
+                      for n, g in ac.items()}
+    return _STEP[key]
+
+
+def _autocast_run(shape):
+    key = ("autocast_run", tuple(shape))
+    if key not in _STEP:
+        _STEP[key] = _oracle_run(shape, "autocast")
+    return _STEP[key]
+
+
+def autocast_buf_err(shape):
+    """{BN running statistic: rel. L2 distance to the fp32 oracle's} of torch's CPU bf16 autocast step"""
+    ref = oracle_step(shape)["bufs"]
+    return {n: rel_err(b, ref[n]) for n, b in _autocast_run(shape)["bufs"].items()}
+
+
+def hip_step(shape, dtype, cuda, loss_scale=1.0):
+    """One HIP train step; loss_scale: the loss is multiplied by it before backward and the gradients
+    divided by it after (a static loss scale, the fp16 recipe)."""
+    from deepfake_amd.pretrained_detector import PretrainedBackboneDetector
+    x, labels = step_inputs(shape)
+    torch.manual_seed(0)
+    det = PretrainedBackboneDetector("efficientnet_b0", pretrained=False, num_classes=2, dropout_rate=0.0,
+                                     compute_dtype=dtype)
+    deterministic_init_(det, seed=STEP_SEED)
+    det = det.to(cuda).train()
+    logits, scores = det(x.to(cuda))
+    loss = torch.nn.functional.cross_entropy(logits, labels.to(cuda), weight=CLASS_W.to(cuda))
+    (loss * loss_scale if loss_scale != 1.0 else loss).backward()
+    torch.cuda.synchronize()
+    grads = {n: p.grad.detach().cpu() / loss_scale for n, p in det.named_parameters()}
+    bufs = {n: b.detach().cpu() for n, b in det.named_buffers() if "running" in n}
+    return logits.detach().cpu(), scores.detach().cpu(), float(loss.detach()), grads, bufs
+
+
+# The 16-bit bound, per tensor: rel_err(HIP 16-bit grad, fp64 oracle grad) <= K * max(rel_err(torch bf16
+# autocast grad, fp64 oracle grad), 1e-3).  torch's autocast (CPU, same oracle module, same inputs and
+# weights) rounds conv inputs / outputs to bf16 like the HIP bf16 step stores its activations, so its
+# error on a tensor measures that tensor's conditioning under bf16 rounding; the HIP step must be no
+# worse than K times it.  K is stated per dtype; the measured worst ratios are printed by every run and
+# recorded in DESIGN.md (round 6).
+K_VS_AUTOCAST = {"bf16": 3.0, "fp16": 1.0}
+AUTOCAST_FLOOR = 1e-3
+FP16_LOSS_SCALE = 1024.0
+
+
+def vs_fp64(shape, dtype, loss, grads, tag=""):
+    """the 16-bit step's loss against the fp32 oracle (2 %) and every gradient against the fp64 oracle
+    within K_VS_AUTOCAST[dtype] x torch-bf16-autocast's error on that tensor"""
+    ref = oracle_step(shape)
+    assert abs(loss - ref["loss"]) <= 2e-2 * abs(ref["loss"]), (loss, ref["loss"])
+    g64, ac = oracle64_step(shape), autocast_err(shape)
+    k = K_VS_AUTOCAST[dtype]
+    scale = max(float(g.norm()) for g in g64.values())
+    rows, bad = [], []
+    for n, r in g64.items():
+        rn = float(r.norm())
+        # structurally ~zero (a BN shift feeding only a training-mode BN): rounding residue only
+        if rn <= 1e-4 * scale:
+            continue
+        e = float((grads[n].double() - r).norm()) / rn
+        anchor = max(ac[n], AUTOCAST_FLOOR)
+        rows.append((e / anchor, n, e, ac[n]))
+        if e > k * anchor:
+            bad.append((n, round(e, 5), round(ac[n], 5)))
+    rows.sort(reverse=True)
+    print(f"{shape}{tag} {dtype}: {len(rows)} gradients; worst err/autocast-err ratios (K = {k}): "
+          + "; ".join(f"{n} {q:.3f} ({e:.2e} vs {a:.2e})" for q, n, e, a in rows[:6]))
+    assert len(rows) >= 0.85 * len(g64)
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------ whole-tensor fp32 gradient check
+# Every element of every fp32 gradient against the fp64 oracle, anchored to torch's own fp32 error:
+#
+#     err_hip(tensor) <= K32 * max(err_torch_fp32(tensor), floor)
+#
+# for two errors per tensor (grad_errors): the relative L2 error of the whole tensor, and -- for
+# tensors with >= 2 dims -- the worst relative L2 error of one dim-0 row (an output channel of a 1x1 /
+# stem / linear weight, one channel of a depthwise weight).  err_torch_fp32 is the same DetectorCPU step
+# in plain torch fp32 on the CPU against the same fp64 run (fp32_anchor), so a tensor that is
+# ill-conditioned in fp32 gets the slack torch itself needs and no more.
+#
+# Floors (the anchors measured on the CPU, torch fp32 against fp64, seed 21, at the four shapes of
+# test_b0_grad_full_gpu.py; none of them from a HIP run):
+#   whole tensor: median anchor 1.1e-5 .. 1.3e-5 per shape, max 5.4e-5 -> TENSOR_FLOOR  = 1e-5
+#   weight rows (85 tensors with >= 2 dims): median 2.7e-5 .. 4.1e-5 per shape -> CHANNEL_FLOOR = 3e-5;
+#     worst row per class: stem 2.7e-5, depthwise 8.7e-5, 1x1 9.5e-5, linear 5.8e-5, SE 1.0e-3 (the SE
+#     expand weight [mid, rd]: rd = 4 .. 48 elements per row, many rows at the 5 % denominator floor)
+#   17 of 219 tensors are structurally zero at every shape (7.8 %).
+# K32 is measured on the MI355X (the HIP step sums in another order than torch): the next power of two
+# at or above twice the worst ratio over every shape and kernel path of test_b0_grad_full_gpu.py and the
+# two 224x224 cases of test_b0_224_gpu.py; the figures are next to the constant.  It is capped by
+# tests/test_grad_checker.py: with this K32 and these floors every planted defect there must be rejected.
+#
+# Measured on the MI355X (err_hip / max(err_torch_fp32, floor); default, forced and split_dw paths):
+#   shape            worst tensor ratio                    worst weight-row ratio
+#   1x2x112x224      1.94  blocks.0.0 bn2.weight           2.86  blocks.4.2 se.conv_reduce.weight
+#   1x2x224x112      1.40  blocks.0.0 bn2.weight           3.02  blocks.5.0 se.conv_expand.weight
+#   1x5x112x112      1.16  blocks.1.0 bn3.weight           2.32  blocks.6.0 se.conv_expand.weight
+#   1x3x100x84       1.95  temporal_attention.2.weight     3.49  blocks.1.0 se.conv_reduce.weight
+#   1x2x224x224      1.39  blocks.1.1 bn3.weight           8.80  blocks.1.0 se.conv_reduce.weight
+#   4x8x224x224      0.82  blocks.3.2 se.conv_reduce.bias  1.38  blocks.3.2 se.conv_expand.weight
+# Every depthwise, 1x1, stem and linear weight row is below 1.9 (the six worst are SE weights).  The 8.80 is one of the four rows of a
+# [4, 96] SE reduce weight at 2 frames: the temporal softmax makes the two frames' terms of that row
+# cancel (row norm under the 5 % denominator floor), so the tensor's whole fp32 error (1.3e-5 of its norm,
+# 1.30 x torch's) lands on a row with a small denominator; torch's own row error there is 6.1e-5.  It sets
+# K32: twice 8.80 is 17.6, the next power of two 32 -- below the smallest planted-defect margin (59).
+TENSOR_FLOOR = 1e-5
+CHANNEL_FLOOR = 3e-5
+K32 = 32.0
+MAX_SKIPPED = 0.10  # at most this share of the tensors may be structurally zero (a condition)
+
+
+def grad_errors(got, ref64):
+    """{name: (tensor error, output-channel error or None)} of the gradients ``got`` against the fp64
+    oracle gradients ``ref64``: the relative L2 error of the whole tensor, and for tensors with >= 2
+    dims the worst relative L2 error over the dim-0 rows, the denominator floored at 5 % of the median
+    row norm (dead rows are judged on the tensor's scale, as _ch_err of test_b0_bench_config_gpu.py)."""
+    out = {}
+    for n, r in ref64.items():
+        r = r.double()
+        d = got[n].double() - r
+        te = float(d.norm()) / (float(r.norm()) + 1e-300)
+        ce = None
+        if r.dim() >= 2:
+            den = r.flatten(1).norm(dim=1)
+            den = torch.maximum(den, 0.05 * den.median())
+            ce = float((d.flatten(1).norm(dim=1) / (den + 1e-300)).max())
+        out[n] = (te, ce)
+    return out
+
+
+def fp32_anchor(shape):
+    """grad_errors of torch's own CPU fp32 oracle step against the fp64 one (cached per shape)"""
+    key = ("anchor32", tuple(shape))
+    if key not in _STEP:
+        _STEP[key] = grad_errors(oracle_step(shape)["grads"], oracle64_step(shape))
+    return _STEP[key]
+
+
+def grad_bound_violations(got, ref64, anchor, k=None, tag=""):
+    """Judge ``got`` by the rule above; returns (violations, worst tensor ratio, worst channel ratio).
+    A ratio is err / max(anchor, floor), to be compared with K32.  Prints the six worst of each."""
+    k = K32 if k is None else k
+    errs = grad_errors(got, ref64)
+    scale = max(float(r.norm()) for r in ref64.values())
+    bad, trows, crows, skipped = [], [], [], 0
+    for n, r in ref64.items():
+        # structurally ~zero (a BN shift feeding only a training-mode BN): rounding residue only
+        if float(r.norm()) <= 1e-4 * scale:
+            skipped += 1
+            continue
+        (te, ce), (ate, ace) = errs[n], anchor[n]
+        ta = max(ate, TENSOR_FLOOR)
+        trows.append((te / ta, n, te, ate))
+        if not te <= k * ta:
+            bad.append((n, "tensor", te, ate))
+        if ce is not None:
+            ca = max(ace, CHANNEL_FLOOR)
+            crows.append((ce / ca, n, ce, ace))
+            if not ce <= k * ca:
+                bad.append((n, "channel", ce, ace))
+    trows.sort(reverse=True)
+    crows.sort(reverse=True)
+    for what, rows in (("tensor", trows), ("channel", crows)):
+        print(f"{tag} fp32 {what} err / torch-fp32 err (K32 = {k}), {len(rows)} tensors, {skipped} skipped: "
+              + "; ".join(f"{n} {q:.2f} ({e:.2e} vs {a:.2e})" for q, n, e, a in rows[:6]))
+    if skipped > MAX_SKIPPED * len(ref64):
+        bad.append(("skipped", skipped, len(ref64)))
+    return bad, (trows[0][0] if trows else 0.0), (crows[0][0] if crows else 0.0)
+
+
+def tensor_class(name, t):
+    """the tensor classes the fp32-vs-fp32 bound below is stated for"""
+    if t.dim() == 1:
+        return "1d"
+    if "conv_dw" in name:
+        return "dw"
+    if ".se." in name:
+        return "se"
+    if t.dim() == 4:
+        return "pw" if t.shape[2] == 1 else "stem"
+    return "linear"
+
+
+# Where only an fp32 oracle exists (256 frames: test_b0_bench_config_gpu.py) both sides carry fp32 error,
+# so the bound on their difference is (K32 + 1) x A, with A the largest torch-fp32-vs-fp64 anchor of the
+# tensor class measured on the CPU at the 32-frame 224x224 case (4 clips x 8 frames, seed 21):
+# class: (whole tensor, worst dim-0 row)
+ANCHOR_B4T8 = {"stem": (2.17e-5, 3.27e-5), "1d": (1.15e-4, None), "dw": (2.22e-5, 8.36e-5),
+               "se": (5.25e-5, 7.84e-4), "pw": (2.19e-5, 5.45e-5), "linear": (1.83e-5, 1.56e-4)}
+
+
+def fp32_pair_violations(got, ref32, tag=""):
+    """``got`` against an fp32 oracle's gradients: whole-tensor and per-row relative L2 difference within
+    (K32 + 1) x ANCHOR_B4T8[class]; returns the violations and prints the six worst ratios of each."""
+    errs = grad_errors(got, ref32)
+    scale = max(float(r.double().norm()) for r in ref32.values())
+    bad, trows, crows = [], [], []
+    for n, r in ref32.items():
+        if float(r.double().norm()) <= 1e-4 * scale:
+            continue
+        at, ac = ANCHOR_B4T8[tensor_class(n, r)]
+        te, ce = errs[n]
+        trows.append((te / at, n, te))
+        if not te <= (K32 + 1) * at:
+            bad.append((n, "tensor", te, at))
+        if ce is not None:
+            crows.append((ce / ac, n, ce))
+            if not ce <= (K32 + 1) * ac:
+                bad.append((n, "channel", ce, ac))
+    for what, rows in (("tensor", trows), ("channel", crows)):
+        rows.sort(reverse=True)
+        print(f"{tag} fp32 {what} difference / class anchor (bound {K32 + 1}): "
+              + "; ".join(f"{n} {q:.2f} ({e:.2e})" for q, n, e in rows[:6]))
+    return bad
+
+
+def check_grads_full(got, shape, tag=""):
+    """every fp32 gradient of a step at ``shape`` against the fp64 oracle, within K32 x torch-fp32's error"""
+    assert sorted(got) == sorted(oracle64_step(shape))
+    bad, _, _ = grad_bound_violations(got, oracle64_step(shape), fp32_anchor(shape), tag=f"{shape}{tag}")
+    assert not bad, bad[:12]

@@ -21,7 +21,9 @@ reference step: ``model(images)`` -> ``CrossEntropyLoss(weight)`` -> ``backward`
 
 Tolerances: fp32 -- logits and loss rtol 1e-3 / atol 1e-5 (north star); every parameter gradient's
 norm within 1e-3 relative and its 64 leading elements within rtol 1e-3 / atol 1e-5 + 1e-3 *
-max|leading|; BN running statistics rtol 1e-4.  16-bit steps (bf16 / fp16 storage, fp32
+max|leading|, and EVERY element through the whole-tensor checker (``b0_helpers.check_grads_full``: per
+tensor and per output channel against the fp64 oracle, within K32 x torch-fp32's own error); BN running
+statistics rtol 1e-4.  16-bit steps (bf16 / fp16 storage, fp32
 accumulation): loss within 2 % of the fp32 oracle, and a PER-TENSOR gradient bound anchored to fp64
 (``_vs_fp64``): every gradient's relative L2 error against the oracle run in float64 must stay within
 K x the error torch's own bf16 autocast of the same oracle step makes on that tensor (floor 1e-3) --
@@ -32,62 +34,37 @@ import numpy as np
 import pytest
 import torch
 
-from b0_helpers import frames
+import b0_helpers
+from b0_helpers import AUTOCAST_FLOOR, CLASS_W, FP16_LOSS_SCALE, K_VS_AUTOCAST  # noqa: F401  (re-exported)
 from deepfake_amd.pretrained_detector import PretrainedBackboneDetector
 from deepfake_amd.weights import deterministic_init_
 from oracle.detector_cpu import DetectorCPU
 
 pytestmark = pytest.mark.gpu
 
-SEED = 21
+SEED = b0_helpers.STEP_SEED
 CASES = {"b1t2": (1, 2), "b4t8": (4, 8)}
-CLASS_W = torch.tensor([0.7, 1.3])
-_ORACLE = {}
+
+
+def _shape(case):
+    return CASES[case] + (224, 224)
 
 
 def _inputs(case):
-    b, t = CASES[case]
-    x = frames(SEED + 1, (b, t, 3, 224, 224))
-    # channels-last strides, as app.py:2084-2086 / train.py:59 hand the frames over
-    x = x.reshape(b * t, 3, 224, 224).contiguous(memory_format=torch.channels_last).view(b, t, 3, 224, 224)
-    labels = torch.tensor([(i * 7 + 1) % 2 for i in range(b)])
-    return x, labels
+    return b0_helpers.step_inputs(_shape(case))
 
 
+# The step, its oracles (fp32, fp64, torch bf16 autocast; cached per shape) and the 16-bit bound live in
+# b0_helpers.py, parameterised by shape (test_b0_grad_full_gpu.py runs them at other shapes).
 def oracle_step(case):
     """fp32 CPU oracle: forward, weighted CE, backward (cached per case)."""
-    if case not in _ORACLE:
-        torch.set_num_threads(max(1, min(16, torch.get_num_threads())))
-        x, labels = _inputs(case)
-        m = DetectorCPU(dropout_rate=0.0)
-        deterministic_init_(m, seed=SEED)
-        m.train()
-        logits, scores = m(x)
-        loss = torch.nn.functional.cross_entropy(logits, labels, weight=CLASS_W)
-        loss.backward()
-        _ORACLE[case] = dict(
-            logits=logits.detach(), scores=scores.detach(), loss=float(loss),
-            grads={n: p.grad.detach().clone() for n, p in m.named_parameters()},
-            bufs={n: b.detach().clone() for n, b in m.named_buffers() if "running" in n})
-    return _ORACLE[case]
+    return b0_helpers.oracle_step(_shape(case))
 
 
 def hip_step(case, dtype, cuda, loss_scale=1.0):
     """One HIP train step; loss_scale: the loss is multiplied by it before backward and the gradients
     divided by it after (a static loss scale, the fp16 recipe)."""
-    x, labels = _inputs(case)
-    torch.manual_seed(0)
-    det = PretrainedBackboneDetector("efficientnet_b0", pretrained=False, num_classes=2, dropout_rate=0.0,
-                                     compute_dtype=dtype)
-    deterministic_init_(det, seed=SEED)
-    det = det.to(cuda).train()
-    logits, scores = det(x.to(cuda))
-    loss = torch.nn.functional.cross_entropy(logits, labels.to(cuda), weight=CLASS_W.to(cuda))
-    (loss * loss_scale if loss_scale != 1.0 else loss).backward()
-    torch.cuda.synchronize()
-    grads = {n: p.grad.detach().cpu() / loss_scale for n, p in det.named_parameters()}
-    bufs = {n: b.detach().cpu() for n, b in det.named_buffers() if "running" in n}
-    return logits.detach().cpu(), scores.detach().cpu(), float(loss), grads, bufs
+    return b0_helpers.hip_step(_shape(case), dtype, cuda, loss_scale)
 
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -113,77 +90,28 @@ def test_train_step_224_fp32(cuda, case, kernel_paths):
             bad.append((n, "head", float((g[:k] - r[:k]).abs().max())))
     print(f"{case}/{kernel_paths}: {len(ref['grads'])} gradients, mismatches {len(bad)}: {bad[:12]}")
     assert not bad
+    # every element of every gradient against the fp64 oracle, within K32 x torch-fp32's own error
+    b0_helpers.check_grads_full(grads, _shape(case), f" {case}/{kernel_paths}")
     for n, rb in ref["bufs"].items():
         torch.testing.assert_close(bufs[n], rb, rtol=1e-4, atol=1e-6, msg=lambda m: f"{n}: {m}")
 
 
-# The 16-bit bound, per tensor: rel_err(HIP 16-bit grad, fp64 oracle grad) <= K * max(rel_err(torch bf16
-# autocast grad, fp64 oracle grad), 1e-3).  torch's autocast (CPU, same oracle module, same inputs and
-# weights) rounds conv inputs / outputs to bf16 like the HIP bf16 step stores its activations, so its
-# error on a tensor measures that tensor's conditioning under bf16 rounding; the HIP step must be no
-# worse than K times it.  K is stated per dtype; the measured worst ratios are printed by every run and
-# recorded in DESIGN.md (round 6).
-K_VS_AUTOCAST = {"bf16": 3.0, "fp16": 1.0}
-AUTOCAST_FLOOR = 1e-3
-FP16_LOSS_SCALE = 1024.0
-_F64, _AC = {}, {}
-
-
+# The 16-bit bound, per tensor (b0_helpers.vs_fp64, K_VS_AUTOCAST): rel_err(HIP 16-bit grad, fp64 oracle
+# grad) <= K * max(rel_err(torch bf16 autocast grad, fp64 oracle grad), 1e-3).
 def oracle64_step(case):
     """the oracle step in float64 on the CPU (inputs, weights and every op in double; cached)"""
-    if case not in _F64:
-        torch.set_num_threads(max(1, min(16, torch.get_num_threads())))
-        x, labels = _inputs(case)
-        m = DetectorCPU(dropout_rate=0.0)
-        deterministic_init_(m, seed=SEED)
-        m = m.double().train()
-        logits, _ = m(x.double())
-        loss = torch.nn.functional.cross_entropy(logits, labels, weight=CLASS_W.double())
-        loss.backward()
-        _F64[case] = {n: p.grad.detach().clone() for n, p in m.named_parameters()}
-    return _F64[case]
+    return b0_helpers.oracle64_step(_shape(case))
 
 
 def autocast_err(case):
     """{tensor: rel. L2 error vs fp64} of torch's CPU bf16 autocast of the oracle step (cached)"""
-    if case not in _AC:
-        g64 = oracle64_step(case)
-        x, labels = _inputs(case)
-        m = DetectorCPU(dropout_rate=0.0)
-        deterministic_init_(m, seed=SEED)
-        m.train()
-        with torch.autocast("cpu", dtype=torch.bfloat16):
-            logits, _ = m(x)
-        torch.nn.functional.cross_entropy(logits.float(), labels, weight=CLASS_W).backward()
-        _AC[case] = {n: float((p.grad.double() - g64[n]).norm()) / (float(g64[n].norm()) + 1e-300)
-                     for n, p in m.named_parameters()}
-    return _AC[case]
+    return b0_helpers.autocast_err(_shape(case))
 
 
 def _vs_fp64(case, dtype, loss, grads, tag=""):
     """the 16-bit step's loss against the fp32 oracle (2 %) and every gradient against the fp64 oracle
     within K_VS_AUTOCAST[dtype] x torch-bf16-autocast's error on that tensor"""
-    ref = oracle_step(case)
-    assert abs(loss - ref["loss"]) <= 2e-2 * abs(ref["loss"]), (loss, ref["loss"])
-    g64, ac = oracle64_step(case), autocast_err(case)
-    k = K_VS_AUTOCAST[dtype]
-    scale = max(float(g.norm()) for g in g64.values())
-    rows, bad = [], []
-    for n, r in g64.items():
-        rn = float(r.norm())
-        # structurally ~zero (a BN shift feeding only a training-mode BN): rounding residue only
-        if rn <= 1e-4 * scale:
-            continue
-        e = float((grads[n].double() - r).norm()) / rn
-        anchor = max(ac[n], AUTOCAST_FLOOR)
-        rows.append((e / anchor, n, e, ac[n]))
-        if e > k * anchor:
-            bad.append((n, round(e, 5), round(ac[n], 5)))
-    rows.sort(reverse=True)
-    print(f"{case}{tag} {dtype}: {len(rows)} gradients; worst err/autocast-err ratios (K = {k}): "
-          + "; ".join(f"{n} {q:.3f} ({e:.2e} vs {a:.2e})" for q, n, e, a in rows[:6]))
-    assert len(rows) >= 0.85 * len(g64)
-    assert not bad, bad
+    b0_helpers.vs_fp64(_shape(case), dtype, loss, grads, f" {case}{tag}")
 
 
 @pytest.mark.parametrize("case", list(CASES))

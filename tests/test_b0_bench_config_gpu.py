@@ -15,7 +15,9 @@ persistent grid.  Three checks:
    so torch's own native conv / BN kernels compute it (no JIT).  Reference step:
    ``model(images)`` -> ``CrossEntropyLoss(weight)`` -> ``backward`` (``src/ensemble_trainer.py:188-198``).
    North-star tolerance: logits / frame scores / loss rtol 1e-3 atol 1e-5; every gradient norm
-   within 1e-3 and its 64 leading elements within rtol 1e-3; BN running stats rtol 1e-4.
+   within 1e-3 and its 64 leading elements within rtol 1e-3; every whole tensor and every output-channel
+   row within (K32 + 1) x the class's torch-fp32-vs-fp64 anchor (``b0_helpers.fp32_pair_violations``);
+   BN running stats rtol 1e-4.
 2. **bf16 step** and the **fp16 step** (loss-scaled; the bench's default dtype) against the same
    fp32 oracle: loss within 2 %; at least 90 % (bf16) / 98 % (fp16) of the gradient tensors within
    10 % in norm and cosine >= 0.98, every tensor cosine >= 0.85 (fp16: >= 0.99).  The per-tensor
@@ -40,6 +42,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from b0_helpers import fp32_pair_violations
 from deepfake_amd import _lib
 from deepfake_amd.pretrained_detector import PretrainedBackboneDetector
 from deepfake_amd.weights import deterministic_init_
@@ -154,6 +157,10 @@ def test_bench_config_fp32_vs_oracle(cuda):
             bad.append((n, "head", float((g[:k] - r[:k]).abs().max())))
     print(f"fp32 256 frames: {len(ref['grads'])} gradients, mismatches {len(bad)}: {bad[:12]}")
     assert not bad
+    # every element: whole-tensor and per-output-channel relative L2 difference to the fp32 oracle within
+    # (K32 + 1) x the class's torch-fp32-vs-fp64 anchor (b0_helpers.ANCHOR_B4T8; no fp64 run at 256 frames)
+    full = fp32_pair_violations(grads, ref["grads"], "256 frames")
+    assert not full, full[:12]
     for n, rb in ref["bufs"].items():
         torch.testing.assert_close(bufs[n], rb, rtol=1e-4, atol=1e-6, msg=lambda m: f"{n}: {m}")
 
