@@ -48,40 +48,75 @@ int launch_pw_fold_bwd(hipStream_t s, const E* g, const E* x, const E* r, const 
 // seams (dfd_pw_conv, dfd_pw_conv_wgrad, dfd_vgemm) install a snapshot of the seam overrides of dfd_set_tuning.
 // Concurrent plans -- e.g. inference on a ThreadPoolExecutor worker (app.py:127-129) next to a
 // training step -- therefore never read each other's knobs.
-enum TuneKey { TK_STREAM_MIN_ROWS = 0, TK_FOLD_MIN_ROWS, TK_DW_BWD_FUSED, TK_GEMM_TILE, TK_DW_BWD1, TK_DW_FWD1,
-               TK_WGRAD_STREAM, TK_MBCONV7, TK_PWL_FUSED, TK_FOLD_FUSED, TK_PW_SK, TK_DW_PF, TK_DW_RB, TK_STEM_OCC, TK_VG_XP,
-               TK_TAIL_FIN, TK_WG_PF, TK_COUNT };
+// One line per knob: key, name (dfd_set_tuning / dfd_b0_plan_set_tuning / bench.py --tune), default.
+#ifndef DFD_VG_XP_DEFAULT  // A/B builds of k_vgemm.o only (tools/ab_lib.sh): the one reader of TK_VG_XP
+#define DFD_VG_XP_DEFAULT 1
+#endif
+#ifndef DFD_TAIL_FIN_DEFAULT
+#define DFD_TAIL_FIN_DEFAULT 15
+#endif
+#ifndef DFD_WG_PF
+#define DFD_WG_PF 1
+#endif
+// clang-format off
+#define DFD_TUNE_KNOBS(X)                                                                                              \
+  /* 1x1 convs with at least this many rows take the streaming kernels (k_pw_stream.hip) */                           \
+  X(TK_STREAM_MIN_ROWS, "stream_min_rows", 40000)                                                                      \
+  /* blocks with at least this many conv_pw rows take the BN-folded backward (bn_fold_pw); below it the extra small   \
+     passes over x cost more than the expanded-tensor passes they save (tests force both paths) */                    \
+  X(TK_FOLD_MIN_ROWS, "fold_min_rows", 100000)                                                                         \
+  /* depthwise data + weight gradient in one kernel (k_dw_bwd.hip) */                                                  \
+  X(TK_DW_BWD_FUSED, "dw_bwd_fused", 1)                                                                                \
+  /* tiled-GEMM config; -1 automatic */                                                                                \
+  X(TK_GEMM_TILE, "gemm_tile", -1)                                                                                     \
+  /* channel-pair stride-1 depthwise backward / forward (k_dw_bwd1.hip, k_dw_fwd1.hip) */                              \
+  X(TK_DW_BWD1, "dw_bwd1", 1)                                                                                          \
+  X(TK_DW_FWD1, "dw_fwd1", 1)                                                                                          \
+  /* the 7x7-stage MBConv forward of the bf16 plan as one fused launch (k_mbconv7.hip); off: measured 394 us per      \
+     block (training) against ~135 us for the unfused launches */                               \
+  X(TK_MBCONV7, "mbconv7", 0)                                                                                          \
+  /* the projection backward of the 16-bit plans as one fused launch (k_pwl_bwd.hip: data gradient, weight gradient   \
+     and the SE + BN2 backward sums; 0 runs the three unfused ones) */                                                 \
+  X(TK_PWL_FUSED, "pwl_fused", 1)                                                                                      \
+  /* the fold path's conv_pw backward of the 16-bit plans as one fused launch (k_pw_fold_bwd.hip: x . Q, the data     \
+     gradient and the three weight-gradient products; 0: unfused) */                                                   \
+  X(TK_FOLD_FUSED, "fold_fused", 1)                                                                                    \
+  /* small-K weight-panel GEMM (k_pw_sk.hip) for K <= 192 */                                                           \
+  X(TK_PW_SK, "pw_sk", 1)                                                                                              \
+  /* depthwise prefetch / row blocking */                                                                              \
+  X(TK_DW_PF, "dw_pf", 1)                                                                                              \
+  X(TK_DW_RB, "dw_rb", 1)                                                                                              \
+  /* stem forward workgroups per CU (120 -> 91 us at 3, profiles/r04 kernel_stats_r04h*) */                            \
+  X(TK_STEM_OCC, "stem_occ", 3)                                                                                        \
+  /* the vgemm NT fragment-pipelined K loop: for the 128-wide tile only (in-model A/B, profiles/r04 ab_vg_xp_r04l:    \
+     the 256-wide form is faster in the L2-warm microbenchmark but not in the ViT step) */                             \
+  X(TK_VG_XP, "vg_xp", DFD_VG_XP_DEFAULT)                                                                              \
+  /* BN finalizes in the producers' last-arriving workgroups (tail.h) instead of their own launches (bit 0: the       \
+     SE-backward chain's BN2 finalize); bit 1: the SE excitation's first product split over its channel slices        \
+     (k_bn.hip SeSplit); bit 2: BN backward finalize inside the apply pass (bn_bwd_apply_fin) where the producer      \
+     wrote <= 256 stat rows; bit 3: forward BN finalize inside the consumer (depthwise forward, SE squeeze, global    \
+     average pool) where the producer wrote <= 128 rows (kBnFinRowsMax) */                                             \
+  X(TK_TAIL_FIN, "tail_fin", DFD_TAIL_FIN_DEFAULT)                                                                     \
+  /* m-steps of loads in flight in the tiled 1x1 weight gradient (pw_wgrad_kernel, bf16) */                            \
+  X(TK_WG_PF, "wg_pf", DFD_WG_PF)
+// clang-format on
+enum TuneKey {
+#define X(key, name, def) key,
+  DFD_TUNE_KNOBS(X)
+#undef X
+  TK_COUNT
+};
 constexpr int64_t kTuneUnset = INT64_MIN;
 struct Tuning {
   int64_t v[TK_COUNT];
   Tuning() { for (auto& x : v) x = kTuneUnset; }
 };
-// defaults: streaming 1x1 kernels from 40,000 rows; BN-folded conv_pw backward from 100,000 rows;
-// fused depthwise backward / channel-pair kernels on; tiled-GEMM config automatic (-1); weight
-// gradients on the main stream; fused 7x7 MBConv off; fused projection / fold backward on; small-K
-// weight-panel GEMM (k_pw_sk.hip) on for K <= 192; depthwise prefetch / row blocking on; the stem
-// forward at 3 workgroups per CU (120 -> 91 us, profiles/r04 kernel_stats_r04h*); the vgemm NT
-// fragment-pipelined K loop for the 128-wide tile only (in-model A/B, profiles/r04 ab_vg_xp_r04l:
-// the 256-wide form is faster in the L2-warm microbenchmark but not in the ViT step)
-#ifndef DFD_VG_XP_DEFAULT  // A/B builds of k_vgemm.o only (tools/ab_lib.sh): the one reader of TK_VG_XP
-#define DFD_VG_XP_DEFAULT 1
-#endif
-// tail_fin: BN finalizes in the producers' last-arriving workgroups (tail.h) instead of their own
-// launches (bit 0: the SE-backward chain's BN2 finalize); bit 1: the SE excitation's first product
-// split over its channel slices (k_bn.hip SeSplit); bit 2: BN backward finalize inside the apply pass
-// (bn_bwd_apply_fin) where the producer wrote <= 256 stat rows; bit 3: forward BN finalize inside the
-// consumer (depthwise forward, SE squeeze, global average pool) where the producer wrote <= 128 rows
-// (kBnFinRowsMax)
-#ifndef DFD_TAIL_FIN_DEFAULT
-#define DFD_TAIL_FIN_DEFAULT 15
-#endif
-// wg_pf: m-steps of loads in flight in the tiled 1x1 weight gradient (pw_wgrad_kernel, bf16)
-#ifndef DFD_WG_PF
-#define DFD_WG_PF 1
-#endif
-constexpr int64_t kTuneDefault[TK_COUNT] = {40000, 100000, 1, -1, 1, 1, 0, 0, 1, 1, 1, 1, 1, 3, DFD_VG_XP_DEFAULT,
-                                            DFD_TAIL_FIN_DEFAULT, DFD_WG_PF};
-extern const char* const kTuneNames[TK_COUNT];
+#define X(key, name, def) def,
+constexpr int64_t kTuneDefault[TK_COUNT] = {DFD_TUNE_KNOBS(X)};
+#undef X
+#define X(key, name, def) name,
+inline constexpr const char* kTuneNames[TK_COUNT] = {DFD_TUNE_KNOBS(X)};
+#undef X
 int64_t tune_override(TuneKey k);  // the calling thread's override, or kTuneUnset
 inline int64_t tune(TuneKey k) {
   const int64_t o = tune_override(k);
@@ -421,9 +456,6 @@ struct SlabJob {
   float* out;
   int splits, accumulate;
 };
-// With an aux stream (the backward's weight-gradient stream), jobs queued from either stream are
-// reduced on `stream`; flush() first makes `stream` wait for everything enqueued on `aux`, and
-// afterwards makes `aux` wait for the reduction (the slab regions are then free on both streams).
 struct SlabDefer {
   static constexpr int kMax = 16;
   hipStream_t stream;
@@ -431,8 +463,6 @@ struct SlabDefer {
   const float* hi;
   SlabJob jobs[kMax];
   int n = 0;
-  hipStream_t aux = nullptr;
-  hipEvent_t ev_aux = nullptr, ev_main = nullptr;
   int flush();
 };
 SlabDefer* set_slab_defer(SlabDefer* d);  // returns the previous one

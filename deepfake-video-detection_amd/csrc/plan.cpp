@@ -201,7 +201,7 @@ int plan_build(Plan& p, int frames, int H, int W, int dtype) {
   alloc_pw(p.head);
   // scratch
   p.stats_cap = (int64_t)2048 * 2 * kHead;
-  p.slab_cap = (int64_t)4 << 20;  // floats per slab region; kSlabRegions regions (see backward_impl)
+  p.slab_cap = (int64_t)4 << 20;  // floats per slab region; kSlabRegions regions (see Backward::slab)
   p.part_cap = std::max<int64_t>((int64_t)4 << 20, 5 * F * std::max<int64_t>(kHead, maxSE));
   p.o_stats = alloc(p.stats_cap * 4);
   p.o_slab = alloc(kSlabRegions * p.slab_cap * 4);
@@ -300,38 +300,8 @@ int probe_read(Plan& p, float* ms, int cap, int* count) {
   return 0;
 }
 
-static void aux_free(Plan& p) {
-  for (auto& e : p.ev)
-    if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  if (p.aux) { (void)hipStreamDestroy(p.aux); p.aux = nullptr; }
-  p.aux_dev = -1;
-}
-
-// the weight-gradient stream on the device of the caller's stream (plans are per device, but the
-// stream of each call is the caller's)
-static int aux_init(Plan& p, hipStream_t s) {
-  int dev = 0;
-  DFD_HIP_CHECK(hipStreamGetDevice(s, &dev));
-  if (p.aux && p.aux_dev == dev) return 0;
-  aux_free(p);
-  int cur = 0;
-  DFD_HIP_CHECK(hipGetDevice(&cur));
-  if (cur != dev) DFD_HIP_CHECK(hipSetDevice(dev));
-  hipError_t e = hipStreamCreateWithFlags(&p.aux, hipStreamNonBlocking);
-  for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&p.ev[i], hipEventDisableTiming);
-  if (cur != dev) (void)hipSetDevice(cur);
-  if (e != hipSuccess) {
-    aux_free(p);
-    set_error((std::string("wgrad stream: ") + hipGetErrorString(e)).c_str(), __FILE__, __LINE__);
-    return -1;
-  }
-  p.aux_dev = dev;
-  return 0;
-}
-
 void plan_free(Plan& p) {
   probe_disarm(p);
-  aux_free(p);
   if (p.cast_dev) { (void)hipFree(p.cast_dev); p.cast_dev = nullptr; }
   if (p.err_host) { (void)hipHostFree(p.err_host); p.err_host = nullptr; }
 }
@@ -362,20 +332,17 @@ inline bool probe_hit(const Plan& p, int kind, const Block* b) {
   return p.probe.kind == kind && p.probe.count < p.probe.n && b && b->stage == p.probe.stage &&
          b->idx == p.probe.idx;
 }
-// Wrap one launch: PROBED(kind, block, launch-expression)
-#define PROBED_ON(KIND, BLK, STREAM, EXPR)                                                 \
-  do {                                                                                     \
-    const bool _hit = probe_hit(p, KIND, BLK);                                             \
-    if (_hit) (void)hipEventRecord(p.probe.b[p.probe.count], STREAM);                      \
-    DFD_TRY(EXPR);                                                                         \
-    if (_hit) { (void)hipEventRecord(p.probe.e[p.probe.count], STREAM); ++p.probe.count; } \
+// Wrap one launch on the plan `p`'s stream `s`: PROBED(kind, block, launch-expression)
+#define PROBED(KIND, BLK, EXPR)                                                      \
+  do {                                                                               \
+    const bool _hit = probe_hit(p, KIND, BLK);                                       \
+    if (_hit) (void)hipEventRecord(p.probe.b[p.probe.count], s);                     \
+    DFD_TRY(EXPR);                                                                   \
+    if (_hit) { (void)hipEventRecord(p.probe.e[p.probe.count], s); ++p.probe.count; } \
   } while (0)
-#define PROBED(KIND, BLK, EXPR) PROBED_ON(KIND, BLK, s, EXPR)
 
-// the fused 7x7-stage MBConv forward (k_mbconv7.hip) for the bf16 plan: knob mbconv7, 0 off (default),
-// 1 on.  Off by default: measured 394 us per block (training) against ~135 us for the unfused launches
-// (six grid barriers at ~14 us each, per-frame weight re-reads from L2).
-// blocks of the 7x7 stages that run as one fused launch (k_mbconv7.hip) in the bf16 forward
+// blocks of the 7x7 stages that run as one fused launch (k_mbconv7.hip) in the bf16 forward: knob
+// mbconv7, off by default (kernels.h)
 static bool block_fused7(const Plan& p, const Block& b) {
   return !b.ds && b.o_s2 >= 0 && tune(TK_MBCONV7) != 0 &&
          mbconv7_supported(p.frames, b.hin, b.win, b.cin, b.mid, b.cout, b.rd, b.k, b.s);
@@ -406,6 +373,53 @@ static InputFmt stem_fmt(const InputFmt& in, const void* x, const int64_t* xs) {
   return o;
 }
 
+// eval mode: every BN's scale / shift from its running statistics in one launch up front, when the
+// offsets fit the table's 32-bit fields.  1 launched, 0 they do not fit (nothing launched), -1 error
+static int bn_eval_all(const Plan& p, hipStream_t s, const float* P, float* bnb, char* ws, float eps) {
+  EvalBnTable t{};
+  bool ok = true;
+  auto add = [&](const BNL& b) {
+    const int64_t v[8] = {p.offs[b.t_w], p.offs[b.t_b], p.offs[b.t_rm], p.offs[b.t_rv],
+                          b.o_mean / 4, b.o_invstd / 4, b.o_scale / 4, b.o_shift / 4};
+    for (int64_t x : v) ok = ok && x >= 0 && x < INT32_MAX;
+    ok = ok && t.n < kEvalBnMax && (b.o_mean | b.o_invstd | b.o_scale | b.o_shift) % 4 == 0;
+    if (!ok) return;
+    t.e[t.n++] = EvalBnEntry{b.C, (int)v[0], (int)v[1], (int)v[2], (int)v[3], (int)v[4], (int)v[5], (int)v[6], (int)v[7]};
+  };
+  add(p.bn_stem);
+  for (const Block& b : p.blocks) {
+    if (!b.ds) add(b.bn1);
+    add(b.ds ? b.bn1 : b.bn2);
+    add(b.bn3);
+  }
+  add(p.bn_head);
+  if (!ok) return 0;
+  DFD_TRY(launch_bn_eval_all(s, P, bnb, reinterpret_cast<float*>(ws), t, eps));
+  return 1;
+}
+
+// one block of the 7x7 stages as ONE launch (k_mbconv7.hip, bf16 plan); `slot`: its barrier counter in o_bar
+static int mbconv7_fwd(const Run<bf16>& r, const Block& b, const bf16* xin, float* bnb, float mom, float eps,
+                       int slot) {
+  const Plan& p = r.p;
+  auto bnp = [&](const BNL& q) {
+    return Mb7Bn{r.prm(q.t_w), r.prm(q.t_b), bnb + p.offs[q.t_rm], bnb + p.offs[q.t_rv], r.f(q.o_mean),
+                 r.f(q.o_invstd), r.f(q.o_scale), r.f(q.o_shift)};
+  };
+  Mb7Args a{};
+  a.frames = p.frames; a.cin = b.cin; a.mid = b.mid; a.cout = b.cout; a.rd = b.rd; a.k = b.k;
+  a.skip = b.skip ? 1 : 0; a.training = r.tr; a.momentum = mom; a.eps = eps;
+  a.x = xin; a.w1 = r.a(b.pw.o_w); a.wdw = r.prm(b.t_dw);
+  a.wr = r.prm(b.t_se_wr); a.br = r.prm(b.t_se_br); a.we = r.prm(b.t_se_we); a.be = r.prm(b.t_se_be);
+  a.w3 = r.a(b.pwl.o_w);
+  a.bn[0] = bnp(b.bn1); a.bn[1] = bnp(b.bn2); a.bn[2] = bnp(b.bn3);
+  a.y1 = r.a(b.o_y1); a.y2 = r.a(b.o_y2); a.s2 = r.a(b.o_s2); a.y3 = r.a(b.o_y3); a.xo = r.a(b.o_x);
+  a.sq = r.f(b.o_sq); a.rpre = r.f(b.o_rpre); a.gate = r.f(b.o_gate); a.part = r.f(p.o_stats);
+  a.bar = reinterpret_cast<unsigned*>(r.ws + p.o_bar) + 4 * slot;
+  a.abort = reinterpret_cast<int*>(r.ws + p.o_bar) + 63;
+  return launch_mbconv7_fwd(r.s, a);
+}
+
 template <typename T>
 int forward_impl(Plan& p, hipStream_t s, const void* x, const int64_t* xs, const InputFmt& in, const float* P,
                  float* bnb, char* ws, float* feat, int tr, float mom) {
@@ -413,31 +427,12 @@ int forward_impl(Plan& p, hipStream_t s, const void* x, const int64_t* xs, const
   const float eps = 1e-5f;
   float* stats = tr ? r.f(p.o_stats) : nullptr;
   int rows = 0;
-  // eval mode: every BN's scale / shift from its running statistics in one launch up front (the
-  // per-layer finalize launches below are skipped), when the offsets fit the table's 32-bit fields
+  // eval mode: one BN launch up front (bn_eval_all); the per-layer finalize launches below are then skipped
   bool eval_all = false;
   if (!tr) {
-    EvalBnTable t{};
-    bool ok = true;
-    auto add = [&](const BNL& b) {
-      const int64_t v[8] = {p.offs[b.t_w], p.offs[b.t_b], p.offs[b.t_rm], p.offs[b.t_rv],
-                            b.o_mean / 4, b.o_invstd / 4, b.o_scale / 4, b.o_shift / 4};
-      for (int64_t x : v) ok = ok && x >= 0 && x < INT32_MAX;
-      ok = ok && t.n < kEvalBnMax && (b.o_mean | b.o_invstd | b.o_scale | b.o_shift) % 4 == 0;
-      if (!ok) return;
-      t.e[t.n++] = EvalBnEntry{b.C, (int)v[0], (int)v[1], (int)v[2], (int)v[3], (int)v[4], (int)v[5], (int)v[6], (int)v[7]};
-    };
-    add(p.bn_stem);
-    for (const Block& b : p.blocks) {
-      if (!b.ds) add(b.bn1);
-      add(b.ds ? b.bn1 : b.bn2);
-      add(b.bn3);
-    }
-    add(p.bn_head);
-    if (ok) {
-      DFD_TRY(launch_bn_eval_all(s, P, bnb, reinterpret_cast<float*>(ws), t, eps));
-      eval_all = true;
-    }
+    const int rc = bn_eval_all(p, s, P, bnb, ws, eps);
+    if (rc < 0) return -1;
+    eval_all = rc == 1;
   }
   auto fin = [&](const BNL& b, int64_t count) {
     if (eval_all) return 0;
@@ -466,7 +461,6 @@ int forward_impl(Plan& p, hipStream_t s, const void* x, const int64_t* xs, const
   DFD_TRY(fin(p.bn_stem, F * p.H1 * p.W1));
   const T* xin = nullptr;
   // fused 7x7-stage blocks (bf16): which blocks take the one-launch path, and their barrier slots
-  auto fused7 = [&](const Block& b) { return is_bf16<T> && block_fused7(p, b); };
   const int nfused = is_bf16<T> ? plan_fused7_blocks(p) : 0;
   if (nfused && tr) DFD_HIP_CHECK(hipMemsetAsync(ws + p.o_bar, 0, kBarBytes, s));
   int slot = 0;
@@ -476,28 +470,12 @@ int forward_impl(Plan& p, hipStream_t s, const void* x, const int64_t* xs, const
     const int hwo = b.hout * b.wout;
     const BNL& bn_dw = b.ds ? b.bn1 : b.bn2;  // BN after the depthwise conv
     DwGeom g{p.frames, b.hin, b.win, b.mid, b.k, b.s, b.k / 2, b.hout, b.wout};
-    if (nfused && fused7(b)) {
-      if constexpr (is_bf16<T>) {
-        auto bnp = [&](const BNL& q) {
-          return Mb7Bn{r.prm(q.t_w), r.prm(q.t_b), bnb + p.offs[q.t_rm], bnb + p.offs[q.t_rv], r.f(q.o_mean),
-                       r.f(q.o_invstd), r.f(q.o_scale), r.f(q.o_shift)};
-        };
-        Mb7Args a{};
-        a.frames = p.frames; a.cin = b.cin; a.mid = b.mid; a.cout = b.cout; a.rd = b.rd; a.k = b.k;
-        a.skip = b.skip ? 1 : 0; a.training = tr; a.momentum = mom; a.eps = eps;
-        a.x = xin; a.w1 = r.a(b.pw.o_w); a.wdw = r.prm(b.t_dw);
-        a.wr = r.prm(b.t_se_wr); a.br = r.prm(b.t_se_br); a.we = r.prm(b.t_se_we); a.be = r.prm(b.t_se_be);
-        a.w3 = r.a(b.pwl.o_w);
-        a.bn[0] = bnp(b.bn1); a.bn[1] = bnp(b.bn2); a.bn[2] = bnp(b.bn3);
-        a.y1 = r.a(b.o_y1); a.y2 = r.a(b.o_y2); a.s2 = r.a(b.o_s2); a.y3 = r.a(b.o_y3); a.xo = r.a(b.o_x);
-        a.sq = r.f(b.o_sq); a.rpre = r.f(b.o_rpre); a.gate = r.f(b.o_gate); a.part = r.f(p.o_stats);
-        a.bar = reinterpret_cast<unsigned*>(ws + p.o_bar) + 4 * slot;
-        a.abort = reinterpret_cast<int*>(ws + p.o_bar) + 63;
-        ++slot;
-        DFD_TRY(launch_mbconv7_fwd(s, a));
+    if constexpr (is_bf16<T>) {
+      if (nfused && block_fused7(p, b)) {
+        DFD_TRY(mbconv7_fwd(r, b, xin, bnb, mom, eps, slot++));
+        xin = r.a(b.o_x);
+        continue;
       }
-      xin = r.a(b.o_x);
-      continue;
     }
     if (b.ds) {
       DFD_TRY(launch_dw_fwd<T>(s, g, r.a(p.o_ystem), r.prm(b.t_dw), r.a(b.o_y2), r.pro_bn(p.bn_stem, b.hin * b.win),
@@ -542,390 +520,402 @@ int forward_impl(Plan& p, hipStream_t s, const void* x, const int64_t* xs, const
   return 0;
 }
 
-// Plan knobs (per plan, dfd_b0_plan_set_tuning; defaults in kTuneDefault):
-// fold_min_rows: blocks with at least this many conv_pw rows take the BN-folded backward
-//   (bn_fold_pw); below it the extra small passes over x cost more than the expanded-tensor passes
-//   they save (tests force both paths);
-// wgrad_stream: 1x1-conv weight gradients on the plan's second stream (0 off, 1 every block, N > 1
-//   blocks with >= N gradient rows).  Off by default: measured 0.17-0.26 ms/step SLOWER at every
-//   threshold (in-process A/B, tools/ab_bench.py) -- the persistent, occupancy-sized depthwise kernels
-//   of the main chain lose resident workgroup slots to the concurrent gradients;
-// pwl_fused: the projection backward of the bf16 plan as one fused launch (k_pwl_bwd.hip: data
-//   gradient, weight gradient and the SE + BN2 backward sums; 0 runs the three unfused ones);
-// fold_fused: the fold path's conv_pw backward of the bf16 plan as one fused launch
-//   (k_pw_fold_bwd.hip: x . Q, the data gradient and the three weight-gradient products; 0: unfused).
+// installs a SlabDefer for the calling thread; the previous one again on exit
+struct DeferScope {
+  SlabDefer* prev;
+  explicit DeferScope(SlabDefer* d) : prev(set_slab_defer(d)) {}
+  ~DeferScope() { set_slab_defer(prev); }
+};
 
+// One backward call (segments [seg_begin, seg_end) on the caller's stream): the state its steps share and one
+// method per step.  Every launch is on `s`: stream order is the only ordering.  A block's steps, in order:
+// projection, excitation, depthwise, expansion.  Scratch sharing (W written by, R read by; free otherwise):
+//   o_gx[i&1] W head_segment / expansion of block i+1 (gradient of block i's output); R projection of block i
+//             (BN3's dZ) and its expansion (skip)
+//   o_stats   (a) W BN3 / head-BN reduce rows; R their finalize (+ apply)
+//             (b) excitation: the first half the BN2 finalize rows (fp64), the second half the split SE
+//                 products; W and R inside that launch
+//             (c) W depthwise: stat rows of the producer's BN (BN1 / stem BN); R expansion (BN1 finalize), or for
+//                 block 0.0 stem_segment (a later call under a segmented backward, see block())
+//             forward: every BN's stat rows; the split SE products between the BN2 finalize and BN3's rows
+//   o_stats2  W / R col_sums (partials and their reduction) in the unfused fold expansion; forward: BN2's stat
+//             rows where the depthwise forward finalizes BN1 itself
+//   o_part    W projection: per-frame SE + BN2 sums; R excitation.  forward: the SE squeeze's sums
+//   o_coef    k1..k3 of one BN at a time, each read before the next step writes it: W BN3 / head-BN finalize, R
+//             the apply or the fused projection; W excitation (BN2), R depthwise; W small expansion (BN1), R its
+//             apply; W stem_segment, R the stem weight gradient
+//   o_coef1   W fold expansion: BN1 finalize; R bn_fold_pw and the combine
+//   o_gs      W BN3 / head-BN apply (g3); R projection / head data + weight gradient.  Then W / R the unfused fold
+//             expansion (x . Q, added by the data gradient that follows)
+//   o_ge2     W projection: data gradient; R SE + BN2 sums, depthwise (its generic path applies BN2 in place)
+//   o_bc      W excitation: squeeze-path gradient; R BN2 finalize, depthwise
+//   o_ge1     W depthwise: data gradient g; R expansion (the small path applies BN1 in place), or for block 0.0
+//             stem_segment
+//   slab      one region per weight gradient in launch order (slab()); R the deferred reduction (defer; the fold
+//             path's own FoldParts); all free after defer.flush(): the call's end, or every region in use
 template <typename T>
-int backward_impl(Plan& p, hipStream_t s, const void* x, const int64_t* xs, const InputFmt& ifmt, const float* dfeat,
-                  const float* P, char* ws, float* G, int tr, int seg_begin, int seg_end, int acc) {
-  Run<T> r{p, s, ws, P, tr};
-  int rows = 0;
-  const int64_t F = p.frames;
-  unsigned* const ctr = reinterpret_cast<unsigned*>(ws + p.o_ctr);  // zeroed by the forward (see plan_build)
-  auto grad = [&](int t) { return G + p.offs[t]; };
+struct Backward {
+  Plan& p;
+  const hipStream_t s;
+  const Run<T> r;
+  float* const G;
+  const bool train, acc;
   // BN backward finalize + apply: one launch (bn_bwd_apply_fin, knob tail_fin bit 2) when the stat rows are
   // few enough for every apply workgroup to reduce its channels' rows itself, else the two launches
-  const bool apply_fin = (tune(TK_TAIL_FIN) & 4) != 0;
-  auto fin_apply = [&](const BnBwdIn& in, const BNL& b, const T* Y, int64_t M, T* out, int nrows, const char* what,
-                       const Block* blk) {
-    int rc = 0;
-    if (apply_fin)
-      rc = launch_bn_bwd_apply_fin<T>(s, in, Y, M, b.C, r.f(p.o_stats), nrows, M, r.prm(b.t_w), r.f(b.o_mean),
-                                      r.f(b.o_invstd), tr != 0, grad(b.t_w), grad(b.t_b), acc != 0, r.f(p.o_coef), out);
-    if (rc < 0) return -1;
-    log_site(rc == 1 ? "bn_bwd_apply_fin" : "bn_bwd_apply", what, blk);
-    if (rc == 1) return 0;
-    DFD_TRY(launch_bn_bwd_finalize(s, r.f(p.o_stats), nrows, M, b.C, r.prm(b.t_w), r.f(b.o_mean), r.f(b.o_invstd),
-                                   tr != 0, grad(b.t_w), grad(b.t_b), acc != 0, r.f(p.o_coef)));
-    DFD_TRY(launch_bn_bwd_apply<T>(s, in, Y, r.f(p.o_coef), out, M, b.C));
-    return 0;
-  };
-  auto bwd_bn = [&](BnBwdIn in, const BNL& b, const T* Y, int64_t M, T* out, const char* what, const Block* blk) {
-    in.mean = r.f(b.o_mean); in.invstd = r.f(b.o_invstd); in.scale = r.f(b.o_scale); in.shift = r.f(b.o_shift);
-    // the fused finalize + apply reads <= 256 stat rows: the reduction takes that cap on the smaller
-    // (late-stage) tensors, where its workgroups still cover the rows in a few passes
-    const int cap = apply_fin && M <= 16384 ? 256 : 0;
-    DFD_TRY(launch_bn_bwd_reduce<T>(s, in, Y, M, b.C, r.f(p.o_stats), &rows, cap));
-    return fin_apply(in, b, Y, M, out, rows, what, blk);
-  };
-  // BN backward when the partials of g, g*xhat are already in o_stats (written by a fused producer)
-  auto bwd_bn_from_stats = [&](BnBwdIn in, const BNL& b, const T* Y, int64_t M, T* out, int nrows, const char* what,
-                               const Block* blk) {
-    in.mean = r.f(b.o_mean); in.invstd = r.f(b.o_invstd); in.scale = r.f(b.o_scale); in.shift = r.f(b.o_shift);
-    return fin_apply(in, b, Y, M, out, nrows, what, blk);
-  };
-  const int nb = (int)p.blocks.size();
-  // the gradient buffer's extent: slab reductions into it are deferred (one launch per segment)
-  int64_t gext = 0;
-  for (size_t t = 0; t < p.tensors.size(); ++t) {
-    if (p.tensors[t].kind != TK_PARAM) continue;
-    int64_t nel = 1;
-    for (int64_t d : p.tensors[t].shape) nel *= d;
-    gext = std::max(gext, p.offs[t] + nel);
-  }
+  const bool apply_fin;
+  unsigned* const ctr;  // zeroed by the forward (see plan_build)
+  int rows = 0;         // out-parameter of the launches that write stat rows
+  // slab reductions into the gradient buffer are deferred (one launch per call, or per kSlabRegions slabs)
   SlabDefer defer{};
-  defer.stream = s;
-  defer.lo = G;
-  defer.hi = G + gext;
-  struct DeferScope {
-    SlabDefer* prev;
-    ~DeferScope() { set_slab_defer(prev); }
-  } scope{set_slab_defer(&defer)};
-  // The 1x1-conv weight gradients run on the plan's second stream `w`, overlapping the main chain
-  // on `s` (BN/SE backward, depthwise backward, data gradients).  Events order the two: w starts
-  // a gradient once its operands are final on s (fork), and s waits for w (join) before it
-  // overwrites a scratch buffer a queued gradient still reads: o_gs (g3, read by the conv_pwl
-  // weight gradient) and o_ge1 / o_coef1 / o_stats2 (the conv_pw weight gradient).  Slab
-  // reductions from both streams are batched on s (SlabDefer joins both ways at every flush).
-  // knob: 0 off; 1 every block; N > 1 only blocks whose gradient rows reach N (the cross-stream
-  // waits cost a few us each: small late-stage gradients are not worth them)
-  const int64_t ws_min = tune(TK_WGRAD_STREAM);
-  hipStream_t w_aux = s;
-  if (ws_min != 0) {
-    DFD_TRY(aux_init(p, s));
-    w_aux = p.aux;
-    defer.aux = w_aux;
-    defer.ev_aux = p.ev[4];
-    defer.ev_main = p.ev[5];
-  }
-  hipStream_t w = s;  // the stream of the current block's weight gradients
-  bool gs_busy = false, ge1_busy = false;
-  auto fork = [&](hipEvent_t ev) -> int {  // w waits for everything enqueued on s so far
-    if (w == s) return 0;
-    DFD_HIP_CHECK(hipEventRecord(ev, s));
-    DFD_HIP_CHECK(hipStreamWaitEvent(w, ev, 0));
-    return 0;
-  };
-  auto mark = [&](hipEvent_t ev, bool& busy) -> int {  // the buffers read on w so far stay busy until ev
-    if (w == s) return 0;
-    DFD_HIP_CHECK(hipEventRecord(ev, w));
-    busy = true;
-    return 0;
-  };
-  auto join = [&](hipEvent_t ev, bool& busy) -> int {  // s waits for the last mark(ev)
-    if (busy) DFD_HIP_CHECK(hipStreamWaitEvent(s, ev, 0));
-    busy = false;
-    return 0;
-  };
+  int region = 0, slab_err = 0;
+  // the SE weight gradients (two small products per block, off the critical chain) are batched into
+  // one launch per call: de / dz stay in per-block buffers until then
   MfmaGemm se_jobs[2 * kMfmaBatch];
   int n_se = 0;
-  auto flush_se = [&]() -> int {
-    const int n = n_se;
-    n_se = 0;
-    return n ? launch_mfma_small_gemm_batch(s, se_jobs, n) : 0;
-  };
-  int region = 0, slab_err = 0;
-  auto slab = [&]() -> float* {
+
+  Backward(Plan& plan, hipStream_t stream, const float* P, char* ws, float* grads, int training, int accumulate)
+      : p(plan), s(stream), r{plan, stream, ws, P, training}, G(grads), train(training != 0), acc(accumulate != 0),
+        apply_fin((tune(TK_TAIL_FIN) & 4) != 0), ctr(reinterpret_cast<unsigned*>(ws + plan.o_ctr)) {
+    int64_t gext = 0;  // the gradient buffer's extent
+    for (size_t t = 0; t < p.tensors.size(); ++t) {
+      if (p.tensors[t].kind != TK_PARAM) continue;
+      int64_t nel = 1;
+      for (int64_t d : p.tensors[t].shape) nel *= d;
+      gext = std::max(gext, p.offs[t] + nel);
+    }
+    defer.stream = s;
+    defer.lo = G;
+    defer.hi = G + gext;
+  }
+
+  float* grad(int t) const { return G + p.offs[t]; }
+  int64_t rows_in(const Block& b) const { return (int64_t)p.frames * b.hin * b.win; }
+  int64_t rows_out(const Block& b) const { return (int64_t)p.frames * b.hout * b.wout; }
+  static const BNL& bn_after_dw(const Block& b) { return b.ds ? b.bn1 : b.bn2; }
+  BnBwdIn with_bn(BnBwdIn in, const BNL& b) const {
+    in.mean = r.f(b.o_mean); in.invstd = r.f(b.o_invstd); in.scale = r.f(b.o_scale); in.shift = r.f(b.o_shift);
+    return in;
+  }
+  float* slab() {
     if (region == kSlabRegions) {  // every region holds a pending slab: reduce them first
       slab_err |= defer.flush();
       region = 0;
     }
     return r.f(p.o_slab) + (int64_t)(region++) * p.slab_cap;
-  };
-  for (int seg = seg_begin; seg < seg_end; ++seg) {
-    if (seg == 0) {
-      const int64_t Mf = F * p.Hf * p.Wf;
-      const Block& last = p.blocks[nb - 1];
-      BnBwdIn in{};
-      in.bc = dfeat; in.bc_scale = 1.0f / (float)(p.Hf * p.Wf); in.rows_per_frame = p.Hf * p.Wf; in.silu = true;
-      DFD_TRY(bwd_bn(in, p.bn_head, r.a(p.o_yh), Mf, r.a(p.o_gs), "bn_head", nullptr));
-      DFD_TRY(launch_pw_gemm<T>(s, r.a(p.o_gs), r.a(p.head.o_wt), r.a(p.o_gx[(nb - 1) & 1]), nullptr, Mf, p.head.cin,
-                                kHead, PRO_NONE, Pro{}, nullptr, nullptr));
-      DFD_TRY(launch_pw_wgrad<T>(s, r.a(p.o_gs), r.a(last.o_x), Mf, kHead, p.head.cin, PRO_NONE, Pro{},
-                                 slab(), p.slab_cap, grad(p.head.t_w), acc != 0));
-    } else if (seg <= 7) {
-      const int st = 7 - seg;
-      for (int i = nb - 1; i >= 0; --i) {
-        const Block& b = p.blocks[i];
-        if (b.stage != st) continue;
-        const int64_t Min = F * b.hin * b.win, Mout = F * b.hout * b.wout;
-        const int hwo = b.hout * b.wout;
-        const BNL& bn_dw = b.ds ? b.bn1 : b.bn2;
-        T* gout = r.a(p.o_gx[i & 1]);
-        DwGeom g{p.frames, b.hin, b.win, b.mid, b.k, b.s, b.k / 2, b.hout, b.wout};
-        w = (ws_min != 0 && Mout >= ws_min) ? w_aux : s;
-        // BN after the 1x1 projection (no activation)
-        BnBwdIn i3{};
-        i3.dZ = gout; i3.rows_per_frame = hwo; i3.silu = false;
-        DFD_TRY(join(p.ev[1], gs_busy));  // the previous conv_pwl weight gradient is done with o_gs
-        int hs = 1, pf = 1;
-        const bool fpwl = is16<T> && tune(TK_PWL_FUSED) != 0 &&
-                          pwl_bwd_covers(p.frames, hwo, b.cout, b.mid);
-        // the BN3 backward applied in the fused kernel's staging pays where the projection is 16 wide
-        // (blocks.0.0: +12 us in the kernel against a 49 us apply pass); at 24 wide the kernel's
-        // extra time exceeds the pass (+29 / +36 us against 18 us, tools/kbench fused)
-        if (fpwl && b.cout <= 16) {
-          // data gradient, weight gradient and the SE + BN2 sums in one pass (k_pwl_bwd.hip), the BN3
-          // backward applied in its staging: only the BN3 reduction + finalize run here
-          i3.mean = r.f(b.bn3.o_mean); i3.invstd = r.f(b.bn3.o_invstd);
-          i3.scale = r.f(b.bn3.o_scale); i3.shift = r.f(b.bn3.o_shift);
-          DFD_TRY(launch_bn_bwd_reduce<T>(s, i3, r.a(b.o_y3), Mout, b.cout, r.f(p.o_stats), &rows));
-          DFD_TRY(launch_bn_bwd_finalize(s, r.f(p.o_stats), rows, Mout, b.cout, r.prm(b.bn3.t_w), r.f(b.bn3.o_mean),
-                                         r.f(b.bn3.o_invstd), tr != 0, grad(b.bn3.t_w), grad(b.bn3.t_b), acc != 0,
-                                         r.f(p.o_coef)));
-          if constexpr (is16<T>) {
-            PROBED(PK_PWL_DGRAD, &b, ((pf = launch_pwl_bwd<T>(s, gout, r.a(b.o_y3), r.f(p.o_coef), r.a(b.pwl.o_wt),
-                                                           r.a(b.o_y2), r.f(bn_dw.o_scale), r.f(bn_dw.o_shift),
-                                                           r.f(bn_dw.o_mean), r.f(bn_dw.o_invstd), r.f(b.o_gate),
-                                                           p.frames, hwo, b.cout, b.mid, r.a(p.o_ge2), slab(),
-                                                           p.slab_cap, grad(b.pwl.t_w), acc != 0, r.f(p.o_part),
-                                                           p.part_cap, &hs)) < 0 ? -1 : 0));
-          }
-          if (pf != 0) {
-            // declined (1: its partial-sum slab or part buffer would not hold this frame count)
-            // or launched without the weight gradient (2): materialise gs with the apply pass for the
-            // unfused launches below
-            DFD_TRY(launch_bn_bwd_apply<T>(s, i3, r.a(b.o_y3), r.f(p.o_coef), r.a(p.o_gs), Mout, b.cout));
-            log_site("bn_bwd_apply", "bn3", &b);
-          }
-        } else {
-          DFD_TRY(bwd_bn(i3, b.bn3, r.a(b.o_y3), Mout, r.a(p.o_gs), "bn3", &b));
-          if (fpwl) {
-            if constexpr (is16<T>) {
-              PROBED(PK_PWL_DGRAD, &b, ((pf = launch_pwl_bwd<T>(s, r.a(p.o_gs), nullptr, nullptr, r.a(b.pwl.o_wt),
-                                                             r.a(b.o_y2), r.f(bn_dw.o_scale), r.f(bn_dw.o_shift),
-                                                             r.f(bn_dw.o_mean), r.f(bn_dw.o_invstd), r.f(b.o_gate),
-                                                             p.frames, hwo, b.cout, b.mid, r.a(p.o_ge2), slab(),
-                                                             p.slab_cap, grad(b.pwl.t_w), acc != 0, r.f(p.o_part),
-                                                             p.part_cap, &hs)) < 0 ? -1 : 0));
-            }
-          }
-        }
-        if (pf == 1) {
-          PROBED(PK_PWL_DGRAD, &b, (launch_pw_gemm<T>(s, r.a(p.o_gs), r.a(b.pwl.o_wt), r.a(p.o_ge2), nullptr, Mout,
-                                                      b.mid, b.cout, PRO_NONE, Pro{}, nullptr, nullptr)));
-        }
-        if (pf != 0) {  // the weight gradient as its own launch (unfused, or the fused kernel without it)
-          const bool mat = b.o_s2 >= 0;
-          DFD_TRY(fork(p.ev[0]));
-          PROBED_ON(PK_PWL_WGRAD, &b, w,
-                    (launch_pw_wgrad<T>(w, r.a(p.o_gs), mat ? r.a(b.o_s2) : r.a(b.o_y2), Mout, b.cout, b.mid,
-                                        mat ? PRO_GATE : PRO_BN_SILU_G, r.pro_bn(bn_dw, hwo, r.f(b.o_gate)), slab(),
-                                        p.slab_cap, grad(b.pwl.t_w), acc != 0)));
-          DFD_TRY(mark(p.ev[1], gs_busy));
-        }
-        if (pf == 1) {
-          // squeeze-excite + the BN+SiLU after the depthwise conv: one pass over (ge2, y2) gives the SE
-          // gate gradient and the per-frame sums of the BN backward (input grad = gated + squeeze path)
-          DFD_TRY(launch_se_bn_bwd_reduce<T>(s, r.a(p.o_ge2), r.a(b.o_y2), r.f(bn_dw.o_scale), r.f(bn_dw.o_shift),
-                                             r.f(bn_dw.o_mean), r.f(bn_dw.o_invstd), p.frames, hwo, b.mid,
-                                             r.f(p.o_part), p.part_cap, &hs));
-        }
-        // the SE weight gradients (two small products per block, off the critical chain) are
-        // batched into one launch per segment: de / dz stay in per-block buffers until then
-        if (n_se + 2 > (int)(sizeof(se_jobs) / sizeof(se_jobs[0]))) DFD_TRY(flush_se());
-        // the BN2 backward finalize (dbeta, dgamma, k1..k3 from gate, bc and the frame sums) in the
-        // excitation launch's last workgroups (knob tail_fin bit 0), o_stats free as row scratch here
-        const bool sefin = (tune(TK_TAIL_FIN) & 1) != 0;
-        // the split excitation's partial products behind the finalize rows in o_stats
-        const SeScratch sesc{ctr + kCtrSe, kCtrAbort - kCtrSe, r.f(p.o_stats) + p.stats_cap / 2,
-                             p.stats_cap / 2, reinterpret_cast<int*>(ctr + kCtrAbort), p.err_host};
-        // (the finalize rows may use only the first half: the split's products sit in the second)
-        const BnFramesFin bnf{reinterpret_cast<double*>(r.f(p.o_stats)), p.stats_cap / 2, ctr, kCtrSe, Mout,
-                              r.prm(bn_dw.t_w), r.f(bn_dw.o_mean), r.f(bn_dw.o_invstd), tr != 0, acc != 0,
-                              grad(bn_dw.t_w), grad(bn_dw.t_b), r.f(p.o_coef)};
-        DFD_TRY(launch_se_fc_bwd(s, r.f(p.o_part), hs, r.f(b.o_gate), r.f(b.o_de), r.f(b.o_sq), r.f(b.o_rpre),
-                                 r.prm(b.t_se_wr), r.prm(b.t_se_we), p.frames, b.mid, b.rd, 1.0f / (float)hwo,
-                                 r.f(b.o_dz), r.f(p.o_bc), grad(b.t_se_wr), grad(b.t_se_br), grad(b.t_se_we),
-                                 grad(b.t_se_be), acc != 0, se_jobs + n_se, sefin ? &bnf : nullptr,
-                                 (tune(TK_TAIL_FIN) & 2) ? &sesc : nullptr));
-        n_se += 2;
-        if (!sefin)
-          DFD_TRY(launch_bn_bwd_finalize_frames(s, r.f(p.o_part), hs, r.f(b.o_gate), r.f(p.o_bc), p.frames, b.mid,
-                                                Mout, r.prm(bn_dw.t_w), r.f(bn_dw.o_mean), r.f(bn_dw.o_invstd),
-                                                tr != 0, grad(bn_dw.t_w), grad(bn_dw.t_b), acc != 0, r.f(p.o_coef)));
-        // depthwise conv
-        // depthwise dgrad fused with the backward reduction of the producer's BN+SiLU
-        // (stem BN for the stage-0 block, bn1 otherwise): ge1 = g, stats = partials of g, g*xhat
-        const BNL& bn_in = b.ds ? p.bn_stem : b.bn1;
-        const T* y_in = b.ds ? r.a(p.o_ystem) : r.a(b.o_y1);
-        BnBwdIn fz{};
-        fz.mean = r.f(bn_in.o_mean); fz.invstd = r.f(bn_in.o_invstd);
-        fz.scale = r.f(bn_in.o_scale); fz.shift = r.f(bn_in.o_shift); fz.silu = true;
-        DFD_TRY(join(p.ev[3], ge1_busy));  // the previous conv_pw weight gradient is done with o_ge1
-        int fused = 1;
-        // stride 1: one kernel also applies the BN2(+SiLU, gate) backward while staging dY
-        // (k_dw_bwd1.hip); otherwise the apply pass materialises dY first
-        if (dw_bwd2_covers(g)) {  // stride 2 (k_dw_bwd2.hip)
-          PROBED(PK_DW_DGRAD, &b, (launch_dw_bwd2<T>(s, g, r.a(p.o_ge2), r.a(b.o_y2), r.f(b.o_gate), r.f(p.o_bc),
-                                                     r.f(bn_dw.o_scale), r.f(bn_dw.o_shift), r.f(p.o_coef),
-                                                     r.prm(b.t_dw), y_in, fz, r.a(p.o_ge1), r.f(p.o_stats), &rows,
-                                                     slab(), p.slab_cap, grad(b.t_dw), acc != 0)));
-          log_site("dw_bwd2", "dw", &b);
-          fused = 0;
-        } else if (dw_bwd1_covers(g)) {
-          PROBED(PK_DW_DGRAD, &b, (launch_dw_bwd1<T>(s, g, r.a(p.o_ge2), r.a(b.o_y2), r.f(b.o_gate), r.f(p.o_bc),
-                                                     r.f(bn_dw.o_scale), r.f(bn_dw.o_shift), r.f(p.o_coef),
-                                                     r.prm(b.t_dw), y_in, fz, r.a(p.o_ge1), r.f(p.o_stats), &rows,
-                                                     slab(), p.slab_cap, grad(b.t_dw), acc != 0)));
-          log_site("dw_bwd1", "dw", &b);
-          fused = 0;
-        } else {
-          BnBwdIn i2{};
-          i2.dZ = r.a(p.o_ge2); i2.gate = r.f(b.o_gate); i2.bc = r.f(p.o_bc); i2.bc_scale = 1.f;
-          i2.rows_per_frame = hwo; i2.silu = true;
-          i2.mean = r.f(bn_dw.o_mean); i2.invstd = r.f(bn_dw.o_invstd);
-          i2.scale = r.f(bn_dw.o_scale); i2.shift = r.f(bn_dw.o_shift);
-          DFD_TRY(launch_bn_bwd_apply<T>(s, i2, r.a(b.o_y2), r.f(p.o_coef), r.a(p.o_ge2), Mout, b.mid));
-          log_site("bn_bwd_apply", "bn2", &b);
-          PROBED(PK_DW_DGRAD, &b, ((fused = launch_dw_bwd<T>(s, g, r.a(p.o_ge2), r.prm(b.t_dw), r.a(p.o_ge1), y_in,
-                                                             &fz, r.f(p.o_stats), &rows, slab(), p.slab_cap,
-                                                             grad(b.t_dw), acc != 0)) < 0 ? -1 : 0));
-        }
-        if (fused == 1) {
-          PROBED(PK_DW_DGRAD, &b, (launch_dw_dgrad<T>(s, g, r.a(p.o_ge2), r.prm(b.t_dw), r.a(p.o_ge1), y_in, &fz,
-                                                      r.f(p.o_stats), &rows)));
-          p.pending_rows = rows;
-          PROBED(PK_DW_WGRAD, &b, (launch_dw_wgrad<T>(s, g, r.a(p.o_ge2), y_in, r.pro_bn(bn_in, b.hin * b.win),
-                                                      PRO_BN_SILU, slab(), p.slab_cap, grad(b.t_dw),
-                                                      acc != 0)));
-        }
-        p.pending_rows = rows;
-        if (!b.ds && Min < tune(TK_FOLD_MIN_ROWS)) {
-          BnBwdIn i1{};
-          i1.dZ = r.a(p.o_ge1); i1.rows_per_frame = b.hin * b.win; i1.silu = false;
-          DFD_TRY(bwd_bn_from_stats(i1, b.bn1, r.a(b.o_y1), Min, r.a(p.o_ge1), p.pending_rows, "bn1", &b));
-          const T* xin = r.a(p.blocks[i - 1].o_x);
-          PROBED(PK_PW_DGRAD, &b, (launch_pw_gemm<T>(s, r.a(p.o_ge1), r.a(b.pw.o_wt), r.a(p.o_gx[(i - 1) & 1]),
-                                                     b.skip ? gout : nullptr, Min, b.cin, b.mid, PRO_NONE, Pro{},
-                                                     nullptr, nullptr)));
-          DFD_TRY(fork(p.ev[2]));
-          PROBED_ON(PK_PW_WGRAD, &b, w, (launch_pw_wgrad<T>(w, r.a(p.o_ge1), xin, Min, b.mid, b.cin, PRO_NONE, Pro{},
-                                                            slab(), p.slab_cap, grad(b.pw.t_w), acc != 0)));
-          DFD_TRY(mark(p.ev[3], ge1_busy));
-        } else if (!b.ds) {
-          // conv_pw + its BN (no activation): ge1 = k1*g + k2*y1 + k3 is never materialised; by
-          // linearity (y1 = x . W^T) the gradients need only g (in ge1) and the block input x:
-          //   dX = g . diag(k1)W + x . W^T diag(k2) W + W^T k3 (+ skip);  dW = diag(k1) g^T x +
-          //   diag(k2) W x^T x + k3 1^T x   (bn_fold_pw, k_bn.hip)
-          const T* xin = r.a(p.blocks[i - 1].o_x);
-          T* gxo = r.a(p.o_gx[(i - 1) & 1]);
-          DFD_TRY(launch_bn_bwd_finalize(s, r.f(p.o_stats), p.pending_rows, Min, b.mid, r.prm(b.bn1.t_w),
-                                         r.f(b.bn1.o_mean), r.f(b.bn1.o_invstd), tr != 0, grad(b.bn1.t_w),
-                                         grad(b.bn1.t_b), acc != 0, r.f(p.o_coef1)));
-          DFD_TRY(launch_bn_fold_pw<T>(s, r.prm(b.pw.t_w), r.f(p.o_coef1), b.mid, b.cin, r.a(p.o_w1t), r.a(p.o_q),
-                                       r.f(p.o_bv)));
-          DFD_TRY(join(p.ev[1], gs_busy));  // the conv_pwl weight gradient is done with o_gs
-          int ff = 1;
-          if (is16<T> && tune(TK_FOLD_FUSED) != 0) {
-            // x . Q, the data gradient and the partial products g^T x, x^T x, 1^T x in one pass
-            // (k_pw_fold_bwd.hip); their three slab reductions as ONE batched launch
-            if constexpr (is16<T>) {
-              float* const parts[3] = {r.f(p.o_tg), r.f(p.o_gram), r.f(p.o_cs)};
-              const int64_t extent[3] = {(int64_t)b.mid * b.cin, (int64_t)b.cin * b.cin, (int64_t)b.cin};
-              SlabDefer loc{};
-              loc.stream = s;
-              loc.lo = parts[0];
-              loc.hi = parts[0] + extent[0];
-              for (int q = 1; q < 3; ++q) {
-                loc.lo = std::min<const float*>(loc.lo, parts[q]);
-                loc.hi = std::max<const float*>(loc.hi, parts[q] + extent[q]);
-              }
-              const DeferScope inner{set_slab_defer(&loc)};
-              PROBED(PK_PW_DGRAD, &b, ((ff = launch_pw_fold_bwd(s, r.a(p.o_ge1), xin, b.skip ? gout : nullptr,
-                                                                r.a(p.o_w1t), r.a(p.o_q), r.f(p.o_bv), gxo, Min,
-                                                                b.mid, b.cin, slab(), p.slab_cap, parts[0], parts[1],
-                                                                parts[2])) < 0 ? -1 : 0));
-              if (ff == 0) DFD_TRY(loc.flush());
-            }
-          }
-          if (ff == 0) {
-            DFD_TRY(launch_pw_wgrad_bn_combine(s, r.f(p.o_tg), r.f(p.o_gram), r.f(p.o_cs), r.prm(b.pw.t_w),
-                                               r.f(p.o_coef1), b.mid, b.cin, grad(b.pw.t_w), acc != 0));
-            continue;
-          }
-          DFD_TRY(launch_tf_gemm<T>(s, xin, r.a(p.o_q), r.a(p.o_gs), b.skip ? gout : nullptr, r.f(p.o_bv), nullptr,
-                                    Min, b.cin, b.cin, PRO_NONE, EPI_BIAS | (b.skip ? EPI_RESID : 0)));
-          PROBED(PK_PW_DGRAD, &b, (launch_pw_gemm<T>(s, r.a(p.o_ge1), r.a(p.o_w1t), gxo, r.a(p.o_gs), Min, b.cin,
-                                                     b.mid, PRO_NONE, Pro{}, nullptr, nullptr)));
-          // the weight gradient through the BN on w: g (o_ge1), x, the BN1 coefficients (o_coef1)
-          DFD_TRY(fork(p.ev[2]));
-          {
-            // the three partial products' slab reductions (into o_tg, o_gram, o_cs) run as ONE
-            // batched launch before the combine reads them
-            float* const parts[3] = {r.f(p.o_tg), r.f(p.o_gram), r.f(p.o_cs)};
-            const int64_t extent[3] = {(int64_t)b.mid * b.cin, (int64_t)b.cin * b.cin, (int64_t)b.cin};
-            SlabDefer loc{};
-            loc.stream = w;
-            loc.lo = parts[0];
-            loc.hi = parts[0] + extent[0];
-            for (int q = 1; q < 3; ++q) {
-              loc.lo = std::min<const float*>(loc.lo, parts[q]);
-              loc.hi = std::max<const float*>(loc.hi, parts[q] + extent[q]);
-            }
-            const DeferScope inner{set_slab_defer(&loc)};  // the segment's defer again on exit
-            PROBED_ON(PK_PW_WGRAD, &b, w, (launch_pw_wgrad<T>(w, r.a(p.o_ge1), xin, Min, b.mid, b.cin, PRO_NONE, Pro{},
-                                                              slab(), p.slab_cap, parts[0], false)));
-            DFD_TRY(launch_pw_wgrad<T>(w, xin, xin, Min, b.cin, b.cin, PRO_NONE, Pro{}, slab(), p.slab_cap, parts[1],
-                                       false));
-            DFD_TRY(launch_col_sums<T>(w, xin, Min, b.cin, r.f(p.o_stats2), p.stats_cap, parts[2]));
-            DFD_TRY(loc.flush());
-          }
-          DFD_TRY(launch_pw_wgrad_bn_combine(w, r.f(p.o_tg), r.f(p.o_gram), r.f(p.o_cs), r.prm(b.pw.t_w),
-                                             r.f(p.o_coef1), b.mid, b.cin, grad(b.pw.t_w), acc != 0));
-          DFD_TRY(mark(p.ev[3], ge1_busy));
-        }
+  }
+  int flush_se() {
+    const int n = n_se;
+    n_se = 0;
+    return n ? launch_mfma_small_gemm_batch(s, se_jobs, n) : 0;
+  }
+  int bn_finalize(const BNL& b, int nrows, int64_t M, float* coef) {
+    return launch_bn_bwd_finalize(s, r.f(p.o_stats), nrows, M, b.C, r.prm(b.t_w), r.f(b.o_mean), r.f(b.o_invstd), train,
+                                  grad(b.t_w), grad(b.t_b), acc, coef);
+  }
+  // BN backward from `nrows` stat rows (partials of g, g*xhat) in o_stats; `in` from with_bn()
+  int fin_apply(const BnBwdIn& in, const BNL& b, const T* Y, int64_t M, T* out, int nrows, const char* what,
+                const Block* blk) {
+    int rc = 0;
+    if (apply_fin)
+      rc = launch_bn_bwd_apply_fin<T>(s, in, Y, M, b.C, r.f(p.o_stats), nrows, M, r.prm(b.t_w), r.f(b.o_mean),
+                                      r.f(b.o_invstd), train, grad(b.t_w), grad(b.t_b), acc, r.f(p.o_coef), out);
+    if (rc < 0) return -1;
+    log_site(rc == 1 ? "bn_bwd_apply_fin" : "bn_bwd_apply", what, blk);
+    if (rc == 1) return 0;
+    DFD_TRY(bn_finalize(b, nrows, M, r.f(p.o_coef)));
+    DFD_TRY(launch_bn_bwd_apply<T>(s, in, Y, r.f(p.o_coef), out, M, b.C));
+    return 0;
+  }
+  int bwd_bn(BnBwdIn in, const BNL& b, const T* Y, int64_t M, T* out, const char* what, const Block* blk) {
+    in = with_bn(in, b);
+    // the fused finalize + apply reads <= 256 stat rows: the reduction takes that cap on the smaller
+    // (late-stage) tensors, where its workgroups still cover the rows in a few passes
+    const int cap = apply_fin && M <= 16384 ? 256 : 0;
+    DFD_TRY(launch_bn_bwd_reduce<T>(s, in, Y, M, b.C, r.f(p.o_stats), &rows, cap));
+    return fin_apply(in, b, Y, M, out, rows, what, blk);
+  }
+
+  int head_segment(const float* dfeat) {
+    const int nb = (int)p.blocks.size();
+    const int64_t Mf = (int64_t)p.frames * p.Hf * p.Wf;
+    const Block& last = p.blocks[nb - 1];
+    BnBwdIn in{};
+    in.bc = dfeat; in.bc_scale = 1.0f / (float)(p.Hf * p.Wf); in.rows_per_frame = p.Hf * p.Wf; in.silu = true;
+    DFD_TRY(bwd_bn(in, p.bn_head, r.a(p.o_yh), Mf, r.a(p.o_gs), "bn_head", nullptr));
+    DFD_TRY(launch_pw_gemm<T>(s, r.a(p.o_gs), r.a(p.head.o_wt), r.a(p.o_gx[(nb - 1) & 1]), nullptr, Mf, p.head.cin,
+                              kHead, PRO_NONE, Pro{}, nullptr, nullptr));
+    DFD_TRY(launch_pw_wgrad<T>(s, r.a(p.o_gs), r.a(last.o_x), Mf, kHead, p.head.cin, PRO_NONE, Pro{},
+                               slab(), p.slab_cap, grad(p.head.t_w), acc));
+    return 0;
+  }
+
+  int block(int i) {
+    const Block& b = p.blocks[i];
+    T* gout = r.a(p.o_gx[i & 1]);
+    int hs = 1;
+    DFD_TRY(projection(b, gout, &hs));
+    DFD_TRY(excitation(b, hs));
+    const int nrows = depthwise(b);
+    if (nrows < 0) return -1;
+    // block 0.0 has no expansion: its stat rows are the stem BN's, finalized by stem_segment -- in a later
+    // call when the backward runs segment by segment, the one case that needs plan state
+    if (b.ds) p.pending_rows = nrows;
+    else DFD_TRY(expansion(b, i, gout, nrows));
+    return 0;
+  }
+
+  // the fused projection backward (k_pwl_bwd.hip: data gradient, weight gradient, SE + BN2 sums) on g = BN3's
+  // input gradient, or with y3 / coef3 on the block's output gradient, the BN3 backward applied in its
+  // staging.  *pf: 0 all done, 1 declined (its partial-sum slab or part buffer would not hold this frame
+  // count), 2 launched without the weight gradient
+  int pwl_fused(const Block& b, const T* g, const T* y3, const float* coef3, int* hs, int* pf) {
+    if constexpr (is16<T>) {
+      const BNL& bn_dw = bn_after_dw(b);
+      PROBED(PK_PWL_DGRAD, &b, ((*pf = launch_pwl_bwd<T>(s, g, y3, coef3, r.a(b.pwl.o_wt), r.a(b.o_y2),
+                                                        r.f(bn_dw.o_scale), r.f(bn_dw.o_shift), r.f(bn_dw.o_mean),
+                                                        r.f(bn_dw.o_invstd), r.f(b.o_gate), p.frames,
+                                                        b.hout * b.wout, b.cout, b.mid, r.a(p.o_ge2), slab(),
+                                                        p.slab_cap, grad(b.pwl.t_w), acc, r.f(p.o_part), p.part_cap,
+                                                        hs)) < 0 ? -1 : 0));
+    }
+    return 0;
+  }
+
+  // BN3 backward (no activation), conv_pwl data + weight gradient, and the per-frame SE + BN2 sums
+  // (o_part, *hs splits per frame)
+  int projection(const Block& b, T* gout, int* hs) {
+    const int64_t Mout = rows_out(b);
+    const int hwo = b.hout * b.wout;
+    const BNL& bn_dw = bn_after_dw(b);
+    BnBwdIn i3{};
+    i3.dZ = gout; i3.rows_per_frame = hwo; i3.silu = false;
+    int pf = 1;
+    const bool fpwl = is16<T> && tune(TK_PWL_FUSED) != 0 && pwl_bwd_covers(p.frames, hwo, b.cout, b.mid);
+    // the BN3 backward applied in the fused kernel's staging pays where the projection is 16 wide
+    // (blocks.0.0: +12 us in the kernel against a 49 us apply pass); at 24 wide the kernel's
+    // extra time exceeds the pass (+29 / +36 us against 18 us, tools/kbench fused)
+    if (fpwl && b.cout <= 16) {
+      // only the BN3 reduction + finalize run here
+      i3 = with_bn(i3, b.bn3);
+      DFD_TRY(launch_bn_bwd_reduce<T>(s, i3, r.a(b.o_y3), Mout, b.cout, r.f(p.o_stats), &rows));
+      DFD_TRY(bn_finalize(b.bn3, rows, Mout, r.f(p.o_coef)));
+      DFD_TRY(pwl_fused(b, gout, r.a(b.o_y3), r.f(p.o_coef), hs, &pf));
+      if (pf != 0) {  // materialise gs with the apply pass for the unfused launches below
+        DFD_TRY(launch_bn_bwd_apply<T>(s, i3, r.a(b.o_y3), r.f(p.o_coef), r.a(p.o_gs), Mout, b.cout));
+        log_site("bn_bwd_apply", "bn3", &b);
       }
     } else {
-      const int64_t M = F * p.H1 * p.W1;
-      // ge1 holds g (the stage-0 depthwise backward fused the BN+SiLU part and the stats); the BN's
-      // dY = k1*g + k2*y + k3 is applied inside the stem weight gradient's tile staging
-      const BNL& b = p.bn_stem;
-      DFD_TRY(launch_bn_bwd_finalize(s, r.f(p.o_stats), p.pending_rows, M, b.C, r.prm(b.t_w), r.f(b.o_mean),
-                                     r.f(b.o_invstd), tr != 0, grad(b.t_w), grad(b.t_b), acc != 0, r.f(p.o_coef)));
-      StemGeom sg{p.frames, p.H, p.W, p.H1, p.W1, xs[0], xs[1], xs[2], xs[3], stem_fmt(ifmt, x, xs)};
-      DFD_TRY(launch_stem_wgrad<T>(s, sg, x, r.a(p.o_ge1), r.a(p.o_ystem), r.f(p.o_coef), slab(), p.slab_cap,
-                                   grad(p.t_stem), acc != 0));
+      DFD_TRY(bwd_bn(i3, b.bn3, r.a(b.o_y3), Mout, r.a(p.o_gs), "bn3", &b));
+      if (fpwl) DFD_TRY(pwl_fused(b, r.a(p.o_gs), nullptr, nullptr, hs, &pf));
     }
-    // this segment's weight gradients are final when the call returns: flushed here unless the call
-    // covers more segments (nobody waits for one; the batches then fill up across segments -- slab()
-    // and the SE batch flush themselves when full)
-    if (seg + 1 == seg_end) {
+    if (pf == 1) {
+      PROBED(PK_PWL_DGRAD, &b, (launch_pw_gemm<T>(s, r.a(p.o_gs), r.a(b.pwl.o_wt), r.a(p.o_ge2), nullptr, Mout,
+                                                  b.mid, b.cout, PRO_NONE, Pro{}, nullptr, nullptr)));
+    }
+    if (pf != 0) {  // the weight gradient as its own launch (unfused, or the fused kernel without it)
+      const bool mat = b.o_s2 >= 0;
+      PROBED(PK_PWL_WGRAD, &b,
+             (launch_pw_wgrad<T>(s, r.a(p.o_gs), mat ? r.a(b.o_s2) : r.a(b.o_y2), Mout, b.cout, b.mid,
+                                 mat ? PRO_GATE : PRO_BN_SILU_G, r.pro_bn(bn_dw, hwo, r.f(b.o_gate)), slab(),
+                                 p.slab_cap, grad(b.pwl.t_w), acc)));
+    }
+    if (pf == 1) {
+      // squeeze-excite + the BN+SiLU after the depthwise conv: one pass over (ge2, y2) gives the SE
+      // gate gradient and the per-frame sums of the BN backward (input grad = gated + squeeze path)
+      DFD_TRY(launch_se_bn_bwd_reduce<T>(s, r.a(p.o_ge2), r.a(b.o_y2), r.f(bn_dw.o_scale), r.f(bn_dw.o_shift),
+                                         r.f(bn_dw.o_mean), r.f(bn_dw.o_invstd), p.frames, hwo, b.mid,
+                                         r.f(p.o_part), p.part_cap, hs));
+    }
+    return 0;
+  }
+
+  // SE FC backward (its two weight-gradient products queued in se_jobs) and the BN2 backward finalize
+  // (dbeta, dgamma, k1..k3 from gate, bc and the frame sums): in the excitation launch's last workgroups
+  // (knob tail_fin bit 0) or as its own launch.  o_stats rows (b) of the table
+  int excitation(const Block& b, int hs) {
+    const int64_t Mout = rows_out(b);
+    const int hwo = b.hout * b.wout;
+    const BNL& bn_dw = bn_after_dw(b);
+    if (n_se + 2 > (int)(sizeof(se_jobs) / sizeof(se_jobs[0]))) DFD_TRY(flush_se());
+    const bool sefin = (tune(TK_TAIL_FIN) & 1) != 0;
+    const SeScratch sesc{ctr + kCtrSe, kCtrAbort - kCtrSe, r.f(p.o_stats) + p.stats_cap / 2,
+                         p.stats_cap / 2, reinterpret_cast<int*>(ctr + kCtrAbort), p.err_host};
+    const BnFramesFin bnf{reinterpret_cast<double*>(r.f(p.o_stats)), p.stats_cap / 2, ctr, kCtrSe, Mout,
+                          r.prm(bn_dw.t_w), r.f(bn_dw.o_mean), r.f(bn_dw.o_invstd), train, acc,
+                          grad(bn_dw.t_w), grad(bn_dw.t_b), r.f(p.o_coef)};
+    DFD_TRY(launch_se_fc_bwd(s, r.f(p.o_part), hs, r.f(b.o_gate), r.f(b.o_de), r.f(b.o_sq), r.f(b.o_rpre),
+                             r.prm(b.t_se_wr), r.prm(b.t_se_we), p.frames, b.mid, b.rd, 1.0f / (float)hwo,
+                             r.f(b.o_dz), r.f(p.o_bc), grad(b.t_se_wr), grad(b.t_se_br), grad(b.t_se_we),
+                             grad(b.t_se_be), acc, se_jobs + n_se, sefin ? &bnf : nullptr,
+                             (tune(TK_TAIL_FIN) & 2) ? &sesc : nullptr));
+    n_se += 2;
+    if (!sefin)
+      DFD_TRY(launch_bn_bwd_finalize_frames(s, r.f(p.o_part), hs, r.f(b.o_gate), r.f(p.o_bc), p.frames, b.mid,
+                                            Mout, r.prm(bn_dw.t_w), r.f(bn_dw.o_mean), r.f(bn_dw.o_invstd),
+                                            train, grad(bn_dw.t_w), grad(bn_dw.t_b), acc, r.f(p.o_coef)));
+    return 0;
+  }
+
+  // depthwise data gradient fused with the backward reduction of the producer's BN+SiLU (stem BN for
+  // block 0.0, bn1 otherwise): ge1 = g, o_stats = partials of g, g*xhat (rows (c) of the table); and the
+  // depthwise weight gradient.  Returns the number of stat rows, -1 on error
+  int depthwise(const Block& b) {
+    const BNL& bn_dw = bn_after_dw(b);
+    const BNL& bn_in = b.ds ? p.bn_stem : b.bn1;
+    const T* y_in = b.ds ? r.a(p.o_ystem) : r.a(b.o_y1);
+    DwGeom g{p.frames, b.hin, b.win, b.mid, b.k, b.s, b.k / 2, b.hout, b.wout};
+    BnBwdIn fz{};
+    fz.silu = true;
+    fz = with_bn(fz, bn_in);
+    int fused = 1;
+    // stride 1: one kernel also applies the BN2(+SiLU, gate) backward while staging dY
+    // (k_dw_bwd1.hip); otherwise the apply pass materialises dY first
+    const bool bwd2 = dw_bwd2_covers(g);  // stride 2 (k_dw_bwd2.hip)
+    if (bwd2 || dw_bwd1_covers(g)) {
+      const auto launch = bwd2 ? launch_dw_bwd2<T> : launch_dw_bwd1<T>;
+      PROBED(PK_DW_DGRAD, &b, (launch(s, g, r.a(p.o_ge2), r.a(b.o_y2), r.f(b.o_gate), r.f(p.o_bc), r.f(bn_dw.o_scale),
+                                      r.f(bn_dw.o_shift), r.f(p.o_coef), r.prm(b.t_dw), y_in, fz, r.a(p.o_ge1),
+                                      r.f(p.o_stats), &rows, slab(), p.slab_cap, grad(b.t_dw), acc)));
+      log_site(bwd2 ? "dw_bwd2" : "dw_bwd1", "dw", &b);
+      fused = 0;
+    } else {
+      BnBwdIn i2{};
+      i2.dZ = r.a(p.o_ge2); i2.gate = r.f(b.o_gate); i2.bc = r.f(p.o_bc); i2.bc_scale = 1.f;
+      i2.rows_per_frame = b.hout * b.wout; i2.silu = true;
+      i2 = with_bn(i2, bn_dw);
+      DFD_TRY(launch_bn_bwd_apply<T>(s, i2, r.a(b.o_y2), r.f(p.o_coef), r.a(p.o_ge2), rows_out(b), b.mid));
+      log_site("bn_bwd_apply", "bn2", &b);
+      PROBED(PK_DW_DGRAD, &b, ((fused = launch_dw_bwd<T>(s, g, r.a(p.o_ge2), r.prm(b.t_dw), r.a(p.o_ge1), y_in,
+                                                         &fz, r.f(p.o_stats), &rows, slab(), p.slab_cap,
+                                                         grad(b.t_dw), acc)) < 0 ? -1 : 0));
+    }
+    if (fused == 1) {  // the data and the weight gradient as two launches
+      PROBED(PK_DW_DGRAD, &b, (launch_dw_dgrad<T>(s, g, r.a(p.o_ge2), r.prm(b.t_dw), r.a(p.o_ge1), y_in, &fz,
+                                                  r.f(p.o_stats), &rows)));
+      PROBED(PK_DW_WGRAD, &b, (launch_dw_wgrad<T>(s, g, r.a(p.o_ge2), y_in, r.pro_bn(bn_in, b.hin * b.win),
+                                                  PRO_BN_SILU, slab(), p.slab_cap, grad(b.t_dw), acc)));
+    }
+    return rows;
+  }
+
+  // conv_pw and its BN (no activation) from g (o_ge1) and the depthwise step's `nrows` stat rows
+  int expansion(const Block& b, int i, const T* gout, int nrows) {
+    const T* xin = r.a(p.blocks[i - 1].o_x);
+    T* gxo = r.a(p.o_gx[(i - 1) & 1]);
+    const T* resid = b.skip ? gout : nullptr;
+    return rows_in(b) < tune(TK_FOLD_MIN_ROWS) ? expansion_small(b, xin, resid, gxo, nrows)
+                                               : expansion_fold(b, xin, resid, gxo, nrows);
+  }
+
+  // BN1 backward applied to ge1 in place, then the two GEMMs
+  int expansion_small(const Block& b, const T* xin, const T* resid, T* gxo, int nrows) {
+    const int64_t Min = rows_in(b);
+    BnBwdIn i1{};
+    i1.dZ = r.a(p.o_ge1); i1.rows_per_frame = b.hin * b.win; i1.silu = false;
+    DFD_TRY(fin_apply(with_bn(i1, b.bn1), b.bn1, r.a(b.o_y1), Min, r.a(p.o_ge1), nrows, "bn1", &b));
+    PROBED(PK_PW_DGRAD, &b, (launch_pw_gemm<T>(s, r.a(p.o_ge1), r.a(b.pw.o_wt), gxo, resid, Min, b.cin, b.mid,
+                                               PRO_NONE, Pro{}, nullptr, nullptr)));
+    PROBED(PK_PW_WGRAD, &b, (launch_pw_wgrad<T>(s, r.a(p.o_ge1), xin, Min, b.mid, b.cin, PRO_NONE, Pro{}, slab(),
+                                                p.slab_cap, grad(b.pw.t_w), acc)));
+    return 0;
+  }
+
+  // The fold path's three partial products g^T x, x^T x, 1^T x (o_tg, o_gram, o_cs).  While one of these is
+  // alive their slab reductions queue on a defer of its own, and flush() runs them as ONE launch, before
+  // the combine reads them; the segment's defer again on exit
+  struct FoldParts {
+    float* at[3];
+    SlabDefer loc{};
+    DeferScope scope;
+    FoldParts(const Backward& w, const Block& b)
+        : at{w.r.f(w.p.o_tg), w.r.f(w.p.o_gram), w.r.f(w.p.o_cs)}, scope(&loc) {
+      const int64_t extent[3] = {(int64_t)b.mid * b.cin, (int64_t)b.cin * b.cin, (int64_t)b.cin};
+      loc.stream = w.s;
+      loc.lo = at[0];
+      loc.hi = at[0] + extent[0];
+      for (int q = 1; q < 3; ++q) {
+        loc.lo = std::min<const float*>(loc.lo, at[q]);
+        loc.hi = std::max<const float*>(loc.hi, at[q] + extent[q]);
+      }
+    }
+    int flush() { return loc.flush(); }
+  };
+
+  // ge1 = k1*g + k2*y1 + k3 is never materialised; by linearity (y1 = x . W^T) the gradients need only g
+  // (in ge1) and the block input x:
+  //   dX = g . diag(k1)W + x . W^T diag(k2) W + W^T k3 (+ skip);  dW = diag(k1) g^T x +
+  //   diag(k2) W x^T x + k3 1^T x   (bn_fold_pw, k_bn.hip)
+  int expansion_fold(const Block& b, const T* xin, const T* resid, T* gxo, int nrows) {
+    const int64_t Min = rows_in(b);
+    DFD_TRY(bn_finalize(b.bn1, nrows, Min, r.f(p.o_coef1)));
+    DFD_TRY(launch_bn_fold_pw<T>(s, r.prm(b.pw.t_w), r.f(p.o_coef1), b.mid, b.cin, r.a(p.o_w1t), r.a(p.o_q),
+                                 r.f(p.o_bv)));
+    int ff = 1;
+    if constexpr (is16<T>) {
+      if (tune(TK_FOLD_FUSED) != 0) {
+        // x . Q, the data gradient and the three partial products in one pass (k_pw_fold_bwd.hip)
+        FoldParts parts(*this, b);
+        PROBED(PK_PW_DGRAD, &b, ((ff = launch_pw_fold_bwd(s, r.a(p.o_ge1), xin, resid, r.a(p.o_w1t), r.a(p.o_q),
+                                                          r.f(p.o_bv), gxo, Min, b.mid, b.cin, slab(), p.slab_cap,
+                                                          parts.at[0], parts.at[1], parts.at[2])) < 0 ? -1 : 0));
+        if (ff == 0) DFD_TRY(parts.flush());
+      }
+    }
+    if (ff != 0) {
+      DFD_TRY(launch_tf_gemm<T>(s, xin, r.a(p.o_q), r.a(p.o_gs), resid, r.f(p.o_bv), nullptr, Min, b.cin, b.cin,
+                                PRO_NONE, EPI_BIAS | (b.skip ? EPI_RESID : 0)));
+      PROBED(PK_PW_DGRAD, &b, (launch_pw_gemm<T>(s, r.a(p.o_ge1), r.a(p.o_w1t), gxo, r.a(p.o_gs), Min, b.cin,
+                                                 b.mid, PRO_NONE, Pro{}, nullptr, nullptr)));
+      FoldParts parts(*this, b);
+      PROBED(PK_PW_WGRAD, &b, (launch_pw_wgrad<T>(s, r.a(p.o_ge1), xin, Min, b.mid, b.cin, PRO_NONE, Pro{}, slab(),
+                                                  p.slab_cap, parts.at[0], false)));
+      DFD_TRY(launch_pw_wgrad<T>(s, xin, xin, Min, b.cin, b.cin, PRO_NONE, Pro{}, slab(), p.slab_cap, parts.at[1],
+                                 false));
+      DFD_TRY(launch_col_sums<T>(s, xin, Min, b.cin, r.f(p.o_stats2), p.stats_cap, parts.at[2]));
+      DFD_TRY(parts.flush());
+    }
+    return launch_pw_wgrad_bn_combine(s, r.f(p.o_tg), r.f(p.o_gram), r.f(p.o_cs), r.prm(b.pw.t_w), r.f(p.o_coef1),
+                                      b.mid, b.cin, grad(b.pw.t_w), acc);
+  }
+
+  // ge1 holds g (block 0.0's depthwise step fused the BN+SiLU part and the stats); the BN's
+  // dY = k1*g + k2*y + k3 is applied inside the stem weight gradient's tile staging
+  int stem_segment(const void* x, const int64_t* xs, const InputFmt& ifmt) {
+    const int64_t M = (int64_t)p.frames * p.H1 * p.W1;
+    DFD_TRY(bn_finalize(p.bn_stem, p.pending_rows, M, r.f(p.o_coef)));
+    StemGeom sg{p.frames, p.H, p.W, p.H1, p.W1, xs[0], xs[1], xs[2], xs[3], stem_fmt(ifmt, x, xs)};
+    return launch_stem_wgrad<T>(s, sg, x, r.a(p.o_ge1), r.a(p.o_ystem), r.f(p.o_coef), slab(), p.slab_cap,
+                                grad(p.t_stem), acc);
+  }
+
+  // a segment's weight gradients are final when the call returns: flushed at the call's last segment
+  // only (nobody waits for an earlier one; the batches then fill up across segments -- slab() and the SE
+  // batch flush themselves when full)
+  int end_segment(bool last) {
+    if (last) {
       DFD_TRY(flush_se());
       DFD_TRY(defer.flush());
       region = 0;
     }
-    DFD_TRY(slab_err);
+    return slab_err;
+  }
+};
+
+template <typename T>
+int backward_impl(Plan& p, hipStream_t s, const void* x, const int64_t* xs, const InputFmt& ifmt, const float* dfeat,
+                  const float* P, char* ws, float* G, int tr, int seg_begin, int seg_end, int acc) {
+  Backward<T> bw(p, s, P, ws, G, tr, acc);
+  const DeferScope scope(&bw.defer);
+  for (int seg = seg_begin; seg < seg_end; ++seg) {
+    if (seg == 0) {
+      DFD_TRY(bw.head_segment(dfeat));
+    } else if (seg <= 7) {  // stage 7 - seg, last block first
+      for (int i = (int)p.blocks.size() - 1; i >= 0; --i)
+        if (p.blocks[i].stage == 7 - seg) DFD_TRY(bw.block(i));
+    } else {
+      DFD_TRY(bw.stem_segment(x, xs, ifmt));
+    }
+    DFD_TRY(bw.end_segment(seg + 1 == seg_end));
   }
   return 0;
 }
@@ -940,10 +930,6 @@ int plan_fused7_blocks(const Plan& p) {
   return n > kBarSlots ? 0 : n;
 }
 
-
-const char* const kTuneNames[TK_COUNT] = {"stream_min_rows", "fold_min_rows", "dw_bwd_fused", "gemm_tile", "dw_bwd1",
-                                          "dw_fwd1", "wgrad_stream", "mbconv7", "pwl_fused", "fold_fused", "pw_sk", "dw_pf", "dw_rb", "stem_occ", "vg_xp",
-                                          "tail_fin", "wg_pf"};
 static thread_local const Tuning* t_tune = nullptr;
 int64_t tune_override(TuneKey k) { return t_tune ? t_tune->v[k] : kTuneUnset; }
 TuningScope::TuningScope(const Tuning* t) : prev(t_tune) { t_tune = t; }

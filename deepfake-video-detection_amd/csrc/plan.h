@@ -74,7 +74,8 @@ struct Plan {
   int64_t o_ystem, o_yh, o_stats, o_slab, o_part, o_coef, o_bc, o_de, o_dz, o_pf;
   int64_t o_gx[2], o_gs, o_ge1, o_ge2;
   int64_t o_w1t, o_q, o_bv, o_tg, o_gram, o_cs;  // conv_pw backward through its BN (bn_fold_pw)
-  int64_t o_coef1, o_stats2;  // BN1 backward coefficients / col_sums partials read on the wgrad stream
+  // BN1 backward coefficients of the fold path; the forward's BN2 stat rows and the fold path's col_sums partials
+  int64_t o_coef1, o_stats2;
   int64_t o_bar;  // grid-barrier counters + abort flag of the fused 7x7 MBConv launches (zeroed per forward)
   int64_t o_ctr;  // kCtrSlots last-arrival / SE slice-barrier counters (zeroed per forward)
   int64_t stats_cap, slab_cap, part_cap;
@@ -83,14 +84,11 @@ struct Plan {
   CastSeg* cast_dev = nullptr;
   int cast_max = 0;
   int device = 0;
-  int pending_rows = 0;  // stat rows written by the stage-0 dw dgrad, consumed by the stem segment
+  // stat rows written by the stage-0 dw dgrad (segment 7), consumed by the stem segment (8): plan state
+  // because a segmented backward runs the two in separate calls
+  int pending_rows = 0;
   Probe probe;
   Tuning tune;  // per-plan kernel-selection overrides (dfd_b0_plan_set_tuning)
-  // the backward's weight-gradient stream (created on first use, on the caller stream's device)
-  // and the events that order it against the caller's stream
-  hipStream_t aux = nullptr;
-  int aux_dev = -1;
-  hipEvent_t ev[6] = {};
   // sticky error word in coherent pinned host memory: a device-side software barrier that timed out
   // (its launch's outputs invalid) sets it; every later forward / backward of the plan then fails
   // (dfd_last_error) until dfd_b0_plan_clear_status -- loud, with no host synchronisation per call

@@ -156,26 +156,6 @@ def test_step_224_bit_reproducible(cuda, dtype):
         assert torch.equal(a[4][n], b[4][n]), n
 
 
-def test_wgrad_stream_bit_identical(cuda):
-    """The 1x1 weight gradients on the plan's second stream (plan knob wgrad_stream = 1; off by default)
-    give bit-identical results to the single-stream schedule: same kernels, same fixed-order
-    reductions; only the overlap changes (a missing event would show up as a race here)."""
-    from deepfake_amd import backbone
-    prev = dict(backbone.DEFAULT_TUNING)
-    try:
-        backbone.DEFAULT_TUNING["wgrad_stream"] = 1
-        _, _, loss_a, grads_a, bufs_a = hip_step("b4t8", "bf16", cuda)
-        backbone.DEFAULT_TUNING["wgrad_stream"] = 0
-        _, _, loss_b, grads_b, bufs_b = hip_step("b4t8", "bf16", cuda)
-    finally:
-        backbone.DEFAULT_TUNING.clear()
-        backbone.DEFAULT_TUNING.update(prev)
-    assert loss_a == loss_b
-    diff = [n for n in grads_a if not torch.equal(grads_a[n], grads_b[n])]
-    assert not diff, diff[:10]
-    assert all(torch.equal(bufs_a[n], bufs_b[n]) for n in bufs_a)
-
-
 @pytest.mark.parametrize("knobs", [{"dw_pf": 1}, {"dw_rb": 1}, {"dw_rb": 2}, {"dw_pf": 1, "dw_rb": 3}])
 def test_depthwise_schedule_knobs_close(cuda, knobs):
     """Depthwise schedule knobs (all off by default) against the default schedule on the bf16 step:

@@ -1,8 +1,8 @@
 // Concurrency probe (development tool): does a late-stage 1x1 weight gradient overlap with the data
 // gradient it is independent of?  For each late-stage pair, the average time per iteration of
 //   serial : dgrad then wgrad on one stream,
-//   2q     : dgrad on stream 1 and wgrad on stream 2 (fork / join events every iteration, the plan's
-//            wgrad_stream pattern),
+//   2q     : dgrad on stream 1 and wgrad on stream 2 (fork / join events every iteration, the pattern
+//            of the plan's former second-stream weight gradients),
 // over back-to-back iterations with HIP events.  build: make -C tools pair_probe (KB_T=f16)
 #include <cstdio>
 #include <cstdlib>
