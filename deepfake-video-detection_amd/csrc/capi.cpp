@@ -649,6 +649,51 @@ int dfd_rn_conv_wgrad(void* stream, const float* x, const int64_t* xs4, int N, i
   DFD_GUARD_END
 }
 
+// ---- test seam: the three convolution launchers with a caller-given fold flag and an optional bias
+// (tests/test_conv_kernels_gpu.py; fold = 0 with a bias are CNNLSTMHybrid's templates, which the
+// dfd_rn_* entry points above never reach).  Product paths do not call these.
+static dfd::ConvGeom test_geom(int N, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int fold) {
+  dfd::ConvGeom g = rn_geom(N, H, W, Cin, Cout, kh, kw, stride, pad);
+  g.fold = fold != 0;
+  return g;
+}
+
+int dfd_test_conv_fwd(void* stream, const float* x, const int64_t* xs4, int N, int H, int W, int Cin, const float* w,
+                      const float* bias, int Cout, int kh, int kw, int stride, int pad, int fold, float* wpack, float* y,
+                      float* stats) {
+  DFD_GUARD_BEGIN
+  if (!x || !xs4 || !w || !wpack || !y || !stats) { dfd::set_error("null argument", __FILE__, __LINE__); return -1; }
+  const dfd::ConvGeom g = test_geom(N, H, W, Cin, Cout, kh, kw, stride, pad, fold);
+  if ((int64_t)N * g.Ho * g.Wo >= (1ll << 31)) { dfd::set_error("test conv: too many rows", __FILE__, __LINE__); return -1; }
+  const int64_t xs[4] = {xs4[0], xs4[1], xs4[2], xs4[3]};
+  int rows = 0;
+  return dfd::conv_forward((hipStream_t)stream, g, x, xs, w, bias, wpack, y, stats, &rows);
+  DFD_GUARD_END
+}
+
+int dfd_test_conv_dgrad(void* stream, const float* dy, int N, int H, int W, int Cin, const float* w, int Cout, int kh,
+                        int kw, int stride, int pad, int fold, float* wpack, float* wpack_t, float* dx) {
+  DFD_GUARD_BEGIN
+  if (!dy || !w || !wpack || !wpack_t || !dx) { dfd::set_error("null argument", __FILE__, __LINE__); return -1; }
+  if ((int64_t)N * H * W >= (1ll << 31)) { dfd::set_error("test conv: too many rows", __FILE__, __LINE__); return -1; }
+  const dfd::ConvGeom g = test_geom(N, H, W, Cin, Cout, kh, kw, stride, pad, fold);
+  return dfd::conv_dgrad((hipStream_t)stream, g, dy, w, wpack, wpack_t, dx);
+  DFD_GUARD_END
+}
+
+int dfd_test_conv_wgrad(void* stream, const float* x, const int64_t* xs4, int N, int H, int W, int Cin, const float* dy,
+                        int Cout, int kh, int kw, int stride, int pad, int fold, float* slab, int64_t slab_floats,
+                        float* dw) {
+  DFD_GUARD_BEGIN
+  if (!x || !xs4 || !dy || !slab || !dw) { dfd::set_error("null argument", __FILE__, __LINE__); return -1; }
+  const dfd::ConvGeom g = test_geom(N, H, W, Cin, Cout, kh, kw, stride, pad, fold);
+  if ((int64_t)N * g.Ho * g.Wo >= (1ll << 31)) { dfd::set_error("test conv: too many rows", __FILE__, __LINE__); return -1; }
+  if ((int64_t)Cout * Cin * kh * kw > slab_floats) { dfd::set_error("test wgrad: slab too small", __FILE__, __LINE__); return -1; }
+  const int64_t xs[4] = {xs4[0], xs4[1], xs4[2], xs4[3]};
+  return dfd::conv_wgrad((hipStream_t)stream, g, x, xs, dy, slab, slab_floats, dw);
+  DFD_GUARD_END
+}
+
 // ---- ResNet-50 training (bf16, k_rn16.hip)
 int dfd_rn16_pack_weights(void* stream, const float* w, int Cout, int Cin, int k, void* wf, void* wd) {
   DFD_GUARD_BEGIN

@@ -131,6 +131,21 @@ DFD_API int dfd_test_occupy(void* stream, int workgroups, int64_t microseconds);
  * device-visible host memory), as it raises the plan status (tests/test_se_sync_gpu.py). */
 DFD_API int dfd_test_group_sync(void* stream, int workgroups, int expected, double seconds, int* scratch,
                                 int* host_word);
+/* Test seam: the fp32 convolution launchers (csrc/k_conv.hip conv_forward / conv_dgrad / conv_wgrad) as
+ * dfd_rn_train_conv_fwd / dfd_rn_conv_dgrad / dfd_rn_conv_wgrad take them, with a caller-given `fold`
+ * (1: the ResNet-50 two-level sums, 0: CNNLSTMHybrid's templates) and, forward only, an optional conv
+ * bias[Cout] added to y before the BN partials (NULL: none).  Buffers as for the dfd_rn_* entry points
+ * (stats: dfd_rn_conv_stat_rows(N, Ho, Wo) * 2 * Cout floats).  No product path calls these
+ * (tests/test_conv_kernels_gpu.py). */
+DFD_API int dfd_test_conv_fwd(void* stream, const float* x, const int64_t* xs4, int N, int H, int W, int Cin,
+                              const float* w, const float* bias, int Cout, int kh, int kw, int stride, int pad,
+                              int fold, float* wpack, float* y, float* stats);
+DFD_API int dfd_test_conv_dgrad(void* stream, const float* dy, int N, int H, int W, int Cin, const float* w, int Cout,
+                                int kh, int kw, int stride, int pad, int fold, float* wpack, float* wpack_t,
+                                float* dx);
+DFD_API int dfd_test_conv_wgrad(void* stream, const float* x, const int64_t* xs4, int N, int H, int W, int Cin,
+                                const float* dy, int Cout, int kh, int kw, int stride, int pad, int fold, float* slab,
+                                int64_t slab_floats, float* dw);
 /* Tensor index range [*lo, *hi) whose gradients are final after segment `seg`. */
 DFD_API int dfd_b0_segment_tensors(int seg, int* lo, int* hi);
 

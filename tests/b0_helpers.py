@@ -296,25 +296,29 @@ def fp32_anchor(shape):
     return _STEP[key]
 
 
-def grad_bound_violations(got, ref64, anchor, k=None, tag=""):
+def grad_bound_violations(got, ref64, anchor, k=None, tag="", tensor_floor=None, channel_floor=None, skip=None):
     """Judge ``got`` by the rule above; returns (violations, worst tensor ratio, worst channel ratio).
-    A ratio is err / max(anchor, floor), to be compared with K32.  Prints the six worst of each."""
+    A ratio is err / max(anchor, floor), to be compared with K32.  Prints the six worst of each.
+    Other models pass their own ``k`` and floors, and ``skip``: the names of their structurally zero
+    tensors -- then exactly those are left out (the caller bounds them) and no norm threshold is used."""
     k = K32 if k is None else k
+    tensor_floor = TENSOR_FLOOR if tensor_floor is None else tensor_floor
+    channel_floor = CHANNEL_FLOOR if channel_floor is None else channel_floor
     errs = grad_errors(got, ref64)
     scale = max(float(r.norm()) for r in ref64.values())
     bad, trows, crows, skipped = [], [], [], 0
     for n, r in ref64.items():
         # structurally ~zero (a BN shift feeding only a training-mode BN): rounding residue only
-        if float(r.norm()) <= 1e-4 * scale:
+        if (n in skip) if skip is not None else (float(r.norm()) <= 1e-4 * scale):
             skipped += 1
             continue
         (te, ce), (ate, ace) = errs[n], anchor[n]
-        ta = max(ate, TENSOR_FLOOR)
+        ta = max(ate, tensor_floor)
         trows.append((te / ta, n, te, ate))
         if not te <= k * ta:
             bad.append((n, "tensor", te, ate))
         if ce is not None:
-            ca = max(ace, CHANNEL_FLOOR)
+            ca = max(ace, channel_floor)
             crows.append((ce / ca, n, ce, ace))
             if not ce <= k * ca:
                 bad.append((n, "channel", ce, ace))
@@ -323,7 +327,7 @@ def grad_bound_violations(got, ref64, anchor, k=None, tag=""):
     for what, rows in (("tensor", trows), ("channel", crows)):
         print(f"{tag} fp32 {what} err / torch-fp32 err (K32 = {k}), {len(rows)} tensors, {skipped} skipped: "
               + "; ".join(f"{n} {q:.2f} ({e:.2e} vs {a:.2e})" for q, n, e, a in rows[:6]))
-    if skipped > MAX_SKIPPED * len(ref64):
+    if skip is None and skipped > MAX_SKIPPED * len(ref64):
         bad.append(("skipped", skipped, len(ref64)))
     return bad, (trows[0][0] if trows else 0.0), (crows[0][0] if crows else 0.0)
 

@@ -94,3 +94,136 @@ def test_planted_defect_is_rejected(step, name, defect, capsys):
     capsys.readouterr()  # the worst-six report is not of interest here
     print(f"{name} {defect.__name__}: margin {max(wt, wc):.1f} (K32 = {bh.K32})")
     assert bad and all(b[0] == name for b in bad), bad
+
+
+# ------------------------------------------------------------------ the CNN-LSTM checker (cnn_lstm_helpers)
+# The same self-test for ``cnn_lstm_helpers.grad_violations`` at 2 x 3 x 40 x 56 (case cl56 of
+# test_cnn_lstm_grad_full_gpu.py): torch's fp32 gradients of the oracle step stand in for the HIP ones, the
+# fp64 run is the reference.  Each planted defect is what one wrong kernel index would produce, and each
+# passes "norm within 1 % + 64 leading elements at 5 %".  A defect is rejected only while its error exceeds
+# K_CL x max(torch-fp32 error, floor), so the smallest margin (error / that anchor) caps K_CL.
+# Measured margins (seed 31): one cnn.4.weight channel x 1.02: 4000 (the smallest); eval cnn.4.bias x 1.05: 2.8e4;
+# cnn.0.bias at 1e-3 of the scale: 3.3e4; one zeroed tap of one cnn.4.weight channel: 3.7e4; two swapped
+# cnn.12.weight channels: 1.2e5; a zeroed classifier.0.weight row: 2.0e5; transposed taps: 5.0e5 (5x5), 3.5e5
+# (3x3); the last step's term of lstm.weight_ih_l1 removed: 4.4e5; the last 82 rows of cnn.8's dY dropped:
+# 8.3e5; f / g gate blocks of lstm.weight_hh_l0 swapped: 2.6e6.
+import cnn_lstm_helpers as ch  # noqa: E402
+
+CL = "cl56"
+CL_DEFECT_CAP = 2048.0  # the power of two below the smallest margin; K_CL may not exceed it (asserted below)
+
+
+def _cl_w12_swap(g, _):
+    g[[470, 505]] = g[[505, 470]]  # two of the last 64 output channels
+
+
+def _cl_w4_scale(g, _):
+    g[97] *= 1.02
+
+
+def _cl_transpose(g, _):
+    g.copy_(g.transpose(2, 3).clone())
+
+
+def _cl_zero_tap(g, _):
+    g[97, :, 2, 0] = 0.0  # one tap of one output channel
+
+
+def _cl_last_tile(g, g64):
+    # cnn.8's weight gradient without its last M % 128 = 82 output pixels (M = 6 x 5 x 7 = 210, NHWC order)
+    def drop(dy):
+        d = dy.permute(0, 2, 3, 1).reshape(-1, dy.shape[1]).clone()
+        d[128:] = 0.0
+        return d.view(dy.shape[0], dy.shape[2], dy.shape[3], dy.shape[1]).permute(0, 3, 1, 2)
+    part = ch.oracle64_dy_hooked(CL, "cnn.8", drop)["grads"]["cnn.8.weight"]
+    g += (part - g64).to(g.dtype)
+
+
+def _cl_gate_swap(g, _):
+    h = g.shape[0] // 4
+    g[h:3 * h] = torch.cat([g[2 * h:3 * h], g[h:2 * h]]).clone()  # f <-> g blocks of (i, f, g, o)
+
+
+def _cl_last_step(g, _):
+    g -= ch.last_step_term(CL, "lstm.weight_ih_l1").to(g.dtype)
+
+
+def _cl_zero_row(g, _):
+    g[77] = 0.0
+
+
+CL_DEFECTS = [("cnn.12.weight", _cl_w12_swap, "train"), ("cnn.4.weight", _cl_w4_scale, "train"),
+              ("cnn.4.weight", _cl_transpose, "train"), ("cnn.8.weight", _cl_transpose, "train"),
+              ("cnn.4.weight", _cl_zero_tap, "train"), ("cnn.8.weight", _cl_last_tile, "train"),
+              ("lstm.weight_hh_l0", _cl_gate_swap, "train"), ("lstm.weight_ih_l1", _cl_last_step, "train"),
+              ("classifier.0.weight", _cl_zero_row, "train")]
+
+
+def test_cl_conditions():
+    """what the checker's inputs must satisfy, on the CPU: pool argmaxes agree between fp32 and fp64, the
+    named structural zeros are zero in fp64, every other gradient is large enough to be judged"""
+    for case in ch.CASES:
+        for mode in (("train", "eval") if case == CL else ("train",)):
+            same, gap = ch.pool_agreement(case, mode)
+            g64 = ch.oracle64(case, mode)["grads"]
+            scale = max(float(g.norm()) for g in g64.values())
+            zs = ch.zeros(case, mode)
+            shares = sorted((float(g.norm()) / scale, n) for n, g in g64.items() if n not in zs)
+            an = ch.anchor(case, mode)
+            worst = max(max(t, c or 0.0) for n, (t, c) in an.items() if n not in zs)
+            print(f"{case}/{mode}: pools agree {same}, top-2 gap {gap:.2e}; smallest shares "
+                  + ", ".join(f"{n} {s:.2e}" for s, n in shares[:3]) + f"; worst anchor {worst:.2e}")
+            assert same
+            assert all(float(g64[n].norm()) <= 1e-12 * scale for n in zs)
+            assert all(s >= (ch.MIN_SHARE_ATT if n.startswith("attention") else ch.MIN_SHARE_OTHER) for s, n in shares)
+            assert worst <= 1e-3  # the condition under which the 16x24 case keeps its size
+
+
+def test_cl_unmodified_fp32_gradients_pass():
+    for mode in ("train", "eval"):
+        bad, wt, wc, wz = ch.grad_violations(ch.oracle(CL, mode)["grads"], CL, mode, tag=" torch fp32")
+        assert not bad, bad
+        assert wt <= 1.0 and wc <= 1.0 and wz <= 1.0  # its own anchor
+
+
+def test_cl_manual_lstm_matches_nn_lstm():
+    """the per-step restatement behind the 'last time step removed' defect is the oracle's LSTM"""
+    g = ch.manual_lstm_grads(CL)
+    ref = ch.oracle64(CL)["grads"]
+    for n in ("lstm.weight_ih_l1", "lstm.weight_hh_l0", "cnn.12.weight"):
+        assert bh.rel_err(g[n], ref[n]) <= 1e-12, n
+
+
+def _cl_margin(got, name, mode, capsys, what):
+    bad, wt, wc, wz = ch.grad_violations(got, CL, mode, tag=f" {name} {what}")
+    capsys.readouterr()
+    m = max(wt, wc, wz)
+    print(f"{name} {what} ({mode}): margin {m:.1f} (K_CL = {ch.K_CL}, cap {CL_DEFECT_CAP})")
+    assert bad and all(b[0] == name for b in bad), bad
+    assert m >= CL_DEFECT_CAP >= ch.K_CL
+    return m
+
+
+@pytest.mark.parametrize("name,defect,mode", CL_DEFECTS, ids=[f"{n}-{d.__name__}" for n, d, _ in CL_DEFECTS])
+def test_cl_planted_defect_is_rejected(name, defect, mode, capsys):
+    g32, g64 = ch.oracle(CL, mode)["grads"], ch.oracle64(CL, mode)["grads"]
+    got = dict(g32)
+    got[name] = g32[name].clone()
+    defect(got[name], g64[name])
+    assert not torch.equal(got[name], g32[name])
+    _cl_margin(got, name, mode, capsys, defect.__name__)
+
+
+def test_cl_planted_bias_defects_are_rejected(capsys):
+    """a structural zero that is not zero (cnn.0.bias at 1e-3 of the scale, training mode), and the real
+    eval-mode conv bias gradient off by 5 %"""
+    g32, g64 = ch.oracle(CL)["grads"], ch.oracle64(CL)["grads"]
+    scale = max(float(g.norm()) for g in g64.values())
+    got = dict(g32)
+    u = torch.ones_like(g32["cnn.0.bias"])
+    got["cnn.0.bias"] = u * (1e-3 * scale / float(u.norm()))
+    _cl_margin(got, "cnn.0.bias", "train", capsys, "1e-3 of the scale")
+    e32 = ch.oracle(CL, "eval")["grads"]
+    got = dict(e32)
+    got["cnn.4.bias"] = e32["cnn.4.bias"] * 1.05
+    _cl_margin(got, "cnn.4.bias", "eval", capsys, "x 1.05")
