@@ -58,7 +58,21 @@ _SIGS = {
     "dfd_test_conv_dgrad": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "dfd_test_conv_wgrad": (c_i, [c_p, c_p, ctypes.POINTER(c_i64), c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i,
                                   c_i, c_p, c_i64, c_p]),
-    "dfd_b0_probe_arm": (c_i, [c_p, c_i, c_i, c_i, c_i]),
+    "dfd_test_vit_bgemm": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, ctypes.POINTER(c_i64), c_p,
+                                 ctypes.POINTER(c_i64), c_p, ctypes.POINTER(c_i64)]),
+    "dfd_test_vit_softmax_fwd": (c_i, [c_p, c_i, c_p, c_p, c_i64, c_i, c_i]),
+    "dfd_test_vit_softmax_bwd": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i64, c_i, c_i, c_f]),
+    "dfd_test_vit_ln_fwd": (c_i, [c_p, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_i, c_f]),
+    "dfd_test_vit_ln_bwd": (c_i, [c_p, c_i, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_p,
+                                  c_i64, c_p, c_p, c_i]),
+    "dfd_test_vit_patch_gather": (c_i, [c_p, c_i, c_p, ctypes.POINTER(c_i64), c_i, c_i, c_i, c_i, c_p]),
+    "dfd_test_vit_tokens_fwd": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "dfd_test_vit_tokens_bwd": (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "dfd_test_vit_wcast": (c_i, [c_p, c_i, c_i, c_fpp, c_fpp, c_fpp, ctypes.POINTER(c_i), ctypes.POINTER(c_i)]),
+    "dfd_test_vit_colsum": (c_i, [c_p, c_i, c_p, c_i64, c_i, c_p, c_i64, c_p, c_i]),
+    "dfd_test_vit_gelu": (c_i, [c_p, c_p, c_p, c_i64, c_i]),
+    "dfd_test_gcn_head_offsets": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_i64)]),
+    "dfd_b0_probe_arm":(c_i, [c_p, c_i, c_i, c_i, c_i]),
     "dfd_b0_probe_read": (c_i, [c_p, ctypes.POINTER(c_f), c_i, ctypes.POINTER(c_i)]),
     "dfd_b0_probe_disarm": (c_i, [c_p]),
     "dfd_b0_segment_tensors": (c_i, [c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i)]),

@@ -694,6 +694,150 @@ int dfd_test_conv_wgrad(void* stream, const float* x, const int64_t* xs4, int N,
   DFD_GUARD_END
 }
 
+// ---- test seam: the launchers of k_vit.hip one by one (tests/test_vit_kernels_gpu.py).  dtype 0 = fp32, 1 = bf16
+// storage; thin calls of the launch_* functions vit.cpp uses.  Product paths do not call these.
+#define VIT_T(dtype, CALL)                                                                     \
+  do {                                                                                         \
+    if ((dtype) == 0) { using T = float; return CALL; }                                        \
+    if ((dtype) == 1) { using T = dfd::bf16; return CALL; }                                    \
+    dfd::set_error("test vit: dtype must be 0 (fp32) or 1 (bf16)", __FILE__, __LINE__);        \
+    return -1;                                                                                 \
+  } while (0)
+
+static dfd::BgOp test_bgop(const int64_t* o) { return dfd::BgOp{o[0], (int)o[1], o[2], o[3]}; }
+
+int dfd_test_vit_bgemm(void* stream, int dtype, int ta, int tb, int batch, int M, int N, int K, float alpha,
+                       const void* A, const int64_t* a4, const void* B, const int64_t* b4, void* C, const int64_t* c4) {
+  DFD_GUARD_BEGIN
+  if (!A || !a4 || !B || !b4 || !C || !c4 || a4[1] < 1 || b4[1] < 1 || c4[1] < 1) {
+    dfd::set_error("test bgemm: null argument or inner < 1", __FILE__, __LINE__);
+    return -1;
+  }
+  VIT_T(dtype, dfd::launch_bgemm<T>((hipStream_t)stream, ta != 0, tb != 0, batch, M, N, K, alpha, (const T*)A,
+                                    test_bgop(a4), (const T*)B, test_bgop(b4), (T*)C, test_bgop(c4)));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_softmax_fwd(void* stream, int dtype, const void* S, void* P, int64_t rows, int n, int ld) {
+  DFD_GUARD_BEGIN
+  if (!S || !P || rows < 1 || n < 1 || n > ld) { dfd::set_error("test softmax: bad argument", __FILE__, __LINE__); return -1; }
+  VIT_T(dtype, dfd::launch_softmax_fwd<T>((hipStream_t)stream, (const T*)S, (T*)P, rows, n, ld));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_softmax_bwd(void* stream, int dtype, const void* P, const void* dP, void* dS, int64_t rows, int n,
+                             int ld, float scale) {
+  DFD_GUARD_BEGIN
+  if (!P || !dP || !dS || rows < 1 || n < 1 || n > ld || ld > 64 * dfd::VIT_SM_PER_LANE) {
+    dfd::set_error("test softmax: bad argument", __FILE__, __LINE__);
+    return -1;
+  }
+  VIT_T(dtype, dfd::launch_softmax_bwd<T>((hipStream_t)stream, (const T*)P, (const T*)dP, (T*)dS, rows, n, ld, scale));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_ln_fwd(void* stream, int dtype, int out_f32, const void* X, int64_t ldx, const float* g,
+                        const float* b, void* Y, int64_t ldy, float* mean, float* rstd, int64_t rows, int C, float eps) {
+  DFD_GUARD_BEGIN
+  if (!X || !g || !b || !Y || !mean || !rstd || rows < 1 || ldx < C || ldy < C) {
+    dfd::set_error("test layernorm: bad argument", __FILE__, __LINE__);
+    return -1;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == 1 && out_f32)
+    return dfd::launch_ln_fwd<dfd::bf16, float>(s, (const dfd::bf16*)X, ldx, g, b, (float*)Y, ldy, mean, rstd, rows, C, eps);
+  VIT_T(dtype, (dfd::launch_ln_fwd<T, T>(s, (const T*)X, ldx, g, b, (T*)Y, ldy, mean, rstd, rows, C, eps)));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_ln_bwd(void* stream, int dtype, int dy_f32, const void* X, int64_t ldx, const void* dY, int64_t ldd,
+                        const float* g, const float* mean, const float* rstd, const void* dres, void* dX, int64_t rows,
+                        int C, float* part, int64_t part_cap, float* dgamma, float* dbeta, int accumulate) {
+  DFD_GUARD_BEGIN
+  if (!X || !dY || !g || !mean || !rstd || !dX || !part || !dgamma || !dbeta || rows < 1 || ldx < C || ldd < C ||
+      part_cap < 2LL * C) {
+    dfd::set_error("test layernorm: bad argument", __FILE__, __LINE__);
+    return -1;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == 1 && dy_f32)
+    return dfd::launch_ln_bwd<dfd::bf16, float>(s, (const dfd::bf16*)X, ldx, (const float*)dY, ldd, g, mean, rstd,
+                                                (const dfd::bf16*)dres, (dfd::bf16*)dX, rows, C, part, part_cap, dgamma,
+                                                dbeta, accumulate != 0);
+  VIT_T(dtype, (dfd::launch_ln_bwd<T, T>(s, (const T*)X, ldx, (const T*)dY, ldd, g, mean, rstd, (const T*)dres, (T*)dX,
+                                         rows, C, part, part_cap, dgamma, dbeta, accumulate != 0)));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_patch_gather(void* stream, int dtype, const float* x, const int64_t* x_strides5, int nodes, int H,
+                              int W, int images, void* A) {
+  DFD_GUARD_BEGIN
+  if (!x || !x_strides5 || !A || nodes < 1 || images < 1 || images % nodes) {
+    dfd::set_error("test patch gather: bad argument", __FILE__, __LINE__);
+    return -1;
+  }
+  const dfd::VitImg im{nodes, H, W, x_strides5[0], x_strides5[1], x_strides5[2], x_strides5[3], x_strides5[4]};
+  VIT_T(dtype, dfd::launch_patch_gather<T>((hipStream_t)stream, x, im, images, (T*)A));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_tokens_fwd(void* stream, int dtype, const void* PE, const float* cls, const float* pos, int images,
+                            int ntok, int D, void* X0) {
+  DFD_GUARD_BEGIN
+  if (!PE || !cls || !pos || !X0 || images < 1 || ntok < 2 || D < 8 || D % 8) {
+    dfd::set_error("test tokens: bad argument", __FILE__, __LINE__);
+    return -1;
+  }
+  VIT_T(dtype, dfd::launch_tokens_fwd<T>((hipStream_t)stream, (const T*)PE, cls, pos, images, ntok, D, (T*)X0));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_tokens_bwd(void* stream, int dtype, const void* dX0, int images, int ntok, int D, void* dPE,
+                            float* dpos, float* dcls) {
+  DFD_GUARD_BEGIN
+  if (!dX0 || !dPE || !dpos || !dcls || images < 1 || ntok < 2 || D < 1) {
+    dfd::set_error("test tokens: bad argument", __FILE__, __LINE__);
+    return -1;
+  }
+  VIT_T(dtype, dfd::launch_tokens_bwd<T>((hipStream_t)stream, (const T*)dX0, images, ntok, D, (T*)dPE, dpos, dcls));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_wcast(void* stream, int dtype, int nseg, const float* const* src, void* const* dst,
+                       void* const* dst_t, const int* rows, const int* cols) {
+  DFD_GUARD_BEGIN
+  if (!src || !dst || !dst_t || !rows || !cols || nseg < 1 || nseg > 8) {
+    dfd::set_error("test wcast: bad argument", __FILE__, __LINE__);
+    return -1;
+  }
+  dfd::VitCast cs{};
+  for (int i = 0; i < nseg; ++i) {
+    if (!src[i] || rows[i] < 1 || cols[i] < 1) { dfd::set_error("test wcast: bad segment", __FILE__, __LINE__); return -1; }
+    cs.seg[i] = {src[i], dst[i], dst_t[i], rows[i], cols[i]};
+  }
+  VIT_T(dtype, dfd::launch_wcast<T>((hipStream_t)stream, cs, nseg));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_colsum(void* stream, int dtype, const void* X, int64_t M, int N, float* part, int64_t part_cap,
+                        float* out, int accumulate) {
+  DFD_GUARD_BEGIN
+  if (!X || !part || !out || M < 1 || N < 8 || part_cap < N) {
+    dfd::set_error("test colsum: bad argument", __FILE__, __LINE__);
+    return -1;
+  }
+  VIT_T(dtype, dfd::launch_colsum<T>((hipStream_t)stream, (const T*)X, M, N, part, part_cap, out, accumulate != 0));
+  DFD_GUARD_END
+}
+
+int dfd_test_vit_gelu(void* stream, void* Z, void* out, int64_t n, int mode) {
+  DFD_GUARD_BEGIN
+  if (!Z || !out) { dfd::set_error("null argument", __FILE__, __LINE__); return -1; }
+  return dfd::launch_gelu((hipStream_t)stream, (dfd::bf16*)Z, (dfd::bf16*)out, n, mode);
+  DFD_GUARD_END
+}
+#undef VIT_T
+
 // ---- ResNet-50 training (bf16, k_rn16.hip)
 int dfd_rn16_pack_weights(void* stream, const float* w, int Cout, int Cin, int k, void* wf, void* wd) {
   DFD_GUARD_BEGIN

@@ -688,6 +688,17 @@ int64_t dfd_gcn_head_scratch_floats(int B, int N, int feat_dim, int hid, int out
   return dfd::head_layout(h).stotal;
 }
 
+// test seam: float offsets of H1, Y1, D1, Y2, G, C1, Dc inside the head's work buffer (head_layout)
+int dfd_test_gcn_head_offsets(int B, int N, int feat_dim, int hid, int out, int num_classes, int64_t* offsets7) {
+  const dfd::HeadDims h{B, N, feat_dim, hid, out, num_classes};
+  if (dfd::head_check(h)) return -1;
+  if (!offsets7) { dfd::set_error("null argument", __FILE__, __LINE__); return -1; }
+  const auto L = dfd::head_layout(h);
+  const int64_t o[7] = {L.H1, L.Y1, L.D1, L.Y2, L.Gm, L.C1, L.Dc};
+  for (int i = 0; i < 7; ++i) offsets7[i] = o[i];
+  return 0;
+}
+
 int dfd_gcn_head_forward(void* stream, int B, int N, int feat_dim, int hid, int out, int num_classes,
                          const float* feats, const float* a_norm, const float* const* params, float* work,
                          int training, uint64_t seed, float p, float* logits) {

@@ -146,6 +146,51 @@ DFD_API int dfd_test_conv_dgrad(void* stream, const float* dy, int N, int H, int
 DFD_API int dfd_test_conv_wgrad(void* stream, const float* x, const int64_t* xs4, int N, int H, int W, int Cin,
                                 const float* dy, int Cout, int kh, int kw, int stride, int pad, int fold, float* slab,
                                 int64_t slab_floats, float* dw);
+/* Test seam: the launchers of csrc/k_vit.hip one at a time, exactly as csrc/vit.cpp calls them
+ * (tests/test_vit_kernels_gpu.py).  dtype 0 = fp32, 1 = bf16 storage of every `void*` operand.  The caller
+ * sizes every buffer; no product path calls these.
+ *  bgemm: C[b] (M x N) = alpha * op(A[b]) (M x K) * op(B[b]) (K x N); ta: A stored [k][m], tb: B stored [n][k];
+ *         a4 / b4 / c4 = (ld, inner, s_outer, s_inner): batch b sits at (b / inner) * s_outer + (b % inner) *
+ *         s_inner elements.  Columns >= N of C are not written.
+ *  softmax: rows of n scores in a row pitch ld <= 256; columns [n, ld) of P and of dS are written as 0.
+ *  ln_fwd / ln_bwd: C % 8 == 0, C <= 1024; ldx is the row pitch of X, dres and dX, ldy / ldd of Y / dY;
+ *         out_f32 / dy_f32 (bf16 only): Y / dY are fp32 (the final norm over the CLS rows).  part: part_cap
+ *         floats (>= 2 C), the number of workgroups is at most part_cap / (2 C).
+ *  patch_gather: A[(image, patch)][c * 256 + ky * 16 + kx] from a (B, nodes, 3, H, W) fp32 batch with element
+ *         strides x_strides5.
+ *  tokens_fwd / tokens_bwd: X0[i][t] = (t == 0 ? cls : PE[i][t - 1]) + pos[t] and its backward.
+ *  wcast: up to 8 segments src[i] fp32 [rows][cols] -> dst[i] [rows][cols] and / or dst_t[i] [cols][rows]
+ *         (either may be NULL).
+ *  colsum: out[n] = sum_m X[m][n], N % 8 == 0, at most part_cap / N row splits.
+ *  gelu (bf16): mode 0: out = gelu(Z), Z := gelu'(Z); mode 1: out *= Z; n % 8 == 0. */
+DFD_API int dfd_test_vit_bgemm(void* stream, int dtype, int ta, int tb, int batch, int M, int N, int K, float alpha,
+                               const void* A, const int64_t* a4, const void* B, const int64_t* b4, void* C,
+                               const int64_t* c4);
+DFD_API int dfd_test_vit_softmax_fwd(void* stream, int dtype, const void* S, void* P, int64_t rows, int n, int ld);
+DFD_API int dfd_test_vit_softmax_bwd(void* stream, int dtype, const void* P, const void* dP, void* dS, int64_t rows,
+                                     int n, int ld, float scale);
+DFD_API int dfd_test_vit_ln_fwd(void* stream, int dtype, int out_f32, const void* X, int64_t ldx, const float* g,
+                                const float* b, void* Y, int64_t ldy, float* mean, float* rstd, int64_t rows, int C,
+                                float eps);
+DFD_API int dfd_test_vit_ln_bwd(void* stream, int dtype, int dy_f32, const void* X, int64_t ldx, const void* dY,
+                                int64_t ldd, const float* g, const float* mean, const float* rstd, const void* dres,
+                                void* dX, int64_t rows, int C, float* part, int64_t part_cap, float* dgamma,
+                                float* dbeta, int accumulate);
+DFD_API int dfd_test_vit_patch_gather(void* stream, int dtype, const float* x, const int64_t* x_strides5, int nodes,
+                                      int H, int W, int images, void* A);
+DFD_API int dfd_test_vit_tokens_fwd(void* stream, int dtype, const void* PE, const float* cls, const float* pos,
+                                    int images, int ntok, int D, void* X0);
+DFD_API int dfd_test_vit_tokens_bwd(void* stream, int dtype, const void* dX0, int images, int ntok, int D, void* dPE,
+                                    float* dpos, float* dcls);
+DFD_API int dfd_test_vit_wcast(void* stream, int dtype, int nseg, const float* const* src, void* const* dst,
+                               void* const* dst_t, const int* rows, const int* cols);
+DFD_API int dfd_test_vit_colsum(void* stream, int dtype, const void* X, int64_t M, int N, float* part,
+                                int64_t part_cap, float* out, int accumulate);
+DFD_API int dfd_test_vit_gelu(void* stream, void* Z, void* out, int64_t n, int mode);
+/* Test seam: float offsets of H1, Y1 (post-ReLU), D1 (after dropout), Y2, G, C1 (post-ReLU), Dc (after dropout)
+ * inside the work buffer of dfd_gcn_head_forward (declared below). */
+DFD_API int dfd_test_gcn_head_offsets(int B, int N, int feat_dim, int hid, int out, int num_classes,
+                                      int64_t* offsets7);
 /* Tensor index range [*lo, *hi) whose gradients are final after segment `seg`. */
 DFD_API int dfd_b0_segment_tensors(int seg, int* lo, int* hi);
 

@@ -269,11 +269,13 @@ K32 = 32.0
 MAX_SKIPPED = 0.10  # at most this share of the tensors may be structurally zero (a condition)
 
 
-def grad_errors(got, ref64):
+def grad_errors(got, ref64, columns=False):
     """{name: (tensor error, output-channel error or None)} of the gradients ``got`` against the fp64
     oracle gradients ``ref64``: the relative L2 error of the whole tensor, and for tensors with >= 2
     dims the worst relative L2 error over the dim-0 rows, the denominator floored at 5 % of the median
-    row norm (dead rows are judged on the tensor's scale, as _ch_err of test_b0_bench_config_gpu.py)."""
+    row norm (dead rows are judged on the tensor's scale, as _ch_err of test_b0_bench_config_gpu.py).
+    ``columns``: the tuples get a third entry, for 2-D tensors the worst relative L2 error over the dim-1
+    columns (an input feature of a linear weight) with the same floored denominator, else None."""
     out = {}
     for n, r in ref64.items():
         r = r.double()
@@ -284,7 +286,15 @@ def grad_errors(got, ref64):
             den = r.flatten(1).norm(dim=1)
             den = torch.maximum(den, 0.05 * den.median())
             ce = float((d.flatten(1).norm(dim=1) / (den + 1e-300)).max())
-        out[n] = (te, ce)
+        if not columns:
+            out[n] = (te, ce)
+            continue
+        ke = None
+        if r.dim() == 2:
+            den = r.norm(dim=0)
+            den = torch.maximum(den, 0.05 * den.median())
+            ke = float((d.norm(dim=0) / (den + 1e-300)).max())
+        out[n] = (te, ce, ke)
     return out
 
 
@@ -296,23 +306,28 @@ def fp32_anchor(shape):
     return _STEP[key]
 
 
-def grad_bound_violations(got, ref64, anchor, k=None, tag="", tensor_floor=None, channel_floor=None, skip=None):
+def grad_bound_violations(got, ref64, anchor, k=None, tag="", tensor_floor=None, channel_floor=None, skip=None,
+                          column_floor=None):
     """Judge ``got`` by the rule above; returns (violations, worst tensor ratio, worst channel ratio).
     A ratio is err / max(anchor, floor), to be compared with K32.  Prints the six worst of each.
     Other models pass their own ``k`` and floors, and ``skip``: the names of their structurally zero
-    tensors -- then exactly those are left out (the caller bounds them) and no norm threshold is used."""
+    tensors -- then exactly those are left out (the caller bounds them) and no norm threshold is used.
+    With ``column_floor`` the dim-1 columns of 2-D tensors are judged too (``anchor`` from
+    ``grad_errors(..., columns=True)``) and the worst column ratio is returned as a fourth value."""
     k = K32 if k is None else k
     tensor_floor = TENSOR_FLOOR if tensor_floor is None else tensor_floor
     channel_floor = CHANNEL_FLOOR if channel_floor is None else channel_floor
-    errs = grad_errors(got, ref64)
+    cols = column_floor is not None
+    errs = grad_errors(got, ref64, columns=cols)
     scale = max(float(r.norm()) for r in ref64.values())
-    bad, trows, crows, skipped = [], [], [], 0
+    bad, trows, crows, krows, skipped = [], [], [], [], 0
     for n, r in ref64.items():
         # structurally ~zero (a BN shift feeding only a training-mode BN): rounding residue only
         if (n in skip) if skip is not None else (float(r.norm()) <= 1e-4 * scale):
             skipped += 1
             continue
-        (te, ce), (ate, ace) = errs[n], anchor[n]
+        te, ce = errs[n][:2]
+        ate, ace = anchor[n][:2]
         ta = max(ate, tensor_floor)
         trows.append((te / ta, n, te, ate))
         if not te <= k * ta:
@@ -322,14 +337,22 @@ def grad_bound_violations(got, ref64, anchor, k=None, tag="", tensor_floor=None,
             crows.append((ce / ca, n, ce, ace))
             if not ce <= k * ca:
                 bad.append((n, "channel", ce, ace))
+        if cols and errs[n][2] is not None:
+            ke, ake = errs[n][2], anchor[n][2]
+            ka = max(ake, column_floor)
+            krows.append((ke / ka, n, ke, ake))
+            if not ke <= k * ka:
+                bad.append((n, "column", ke, ake))
     trows.sort(reverse=True)
     crows.sort(reverse=True)
-    for what, rows in (("tensor", trows), ("channel", crows)):
+    krows.sort(reverse=True)
+    for what, rows in (("tensor", trows), ("channel", crows)) + ((("column", krows),) if cols else ()):
         print(f"{tag} fp32 {what} err / torch-fp32 err (K32 = {k}), {len(rows)} tensors, {skipped} skipped: "
               + "; ".join(f"{n} {q:.2f} ({e:.2e} vs {a:.2e})" for q, n, e, a in rows[:6]))
     if skip is None and skipped > MAX_SKIPPED * len(ref64):
         bad.append(("skipped", skipped, len(ref64)))
-    return bad, (trows[0][0] if trows else 0.0), (crows[0][0] if crows else 0.0)
+    worst = (trows[0][0] if trows else 0.0), (crows[0][0] if crows else 0.0)
+    return (bad, *worst, (krows[0][0] if krows else 0.0)) if cols else (bad, *worst)
 
 
 def tensor_class(name, t):
