@@ -5,6 +5,8 @@ Drop-in counterparts of the reference's hot-path API (SaiPranav1506/DeepFake-Vid
 * ``PretrainedBackboneDetector`` / ``EnsembleDetector``  (src/pretrained_detector.py)
 * ``EfficientNetB0Trunk`` / ``B0FrameExtractor``         (the timm trunk, src/pretrained_detector.py:43-46)
 * ``WeightedCrossEntropyLoss``                           (nn.CrossEntropyLoss(weight), ensemble_trainer.py:358)
+* ``FocalLoss`` / ``SmoothedCrossEntropyLoss``             (train_improved.py:29-78, 136-150)
+* ``ImprovedTrainStep``                                   (ImprovedTrainer's step, train_improved.py:104-232)
 * ``FusedAdamW`` / ``FusedAdam`` / ``clip_grad_norm_``     (ensemble_trainer.py:146,199-200; train.py:323)
 * ``train_step`` / ``DataParallelTrainer``                 (EnsembleTrainer.train_epoch step, ensemble_trainer.py:182-200)
 * ``LogicRNNLSTM`` / ``LogicCell`` / ``create_model``       (src/RNNModel.py)
@@ -19,7 +21,8 @@ Submodules import lazily so ``import deepfake_amd`` works before the library is 
 __all__ = [
     "PretrainedBackboneDetector", "EnsembleDetector", "EfficientNetB0Trunk", "B0FrameExtractor",
     "WeightedCrossEntropyLoss", "FusedAdamW", "FusedAdam", "clip_grad_norm_", "LogicRNNLSTM", "LogicCell",
-    "create_model", "CNNLSTMHybrid", "DeepfakeModel", "ViTFeatureExtractor", "SimpleGCN",
+    "create_model", "CNNLSTMHybrid", "DeepfakeModel", "ViTFeatureExtractor", "SimpleGCN", "FocalLoss",
+    "SmoothedCrossEntropyLoss", "ImprovedTrainStep",
 ]
 
 
@@ -28,8 +31,10 @@ def __getattr__(name):
         from . import pretrained_detector as m
     elif name in ("EfficientNetB0Trunk", "B0FrameExtractor"):
         from . import backbone as m
-    elif name == "WeightedCrossEntropyLoss":
+    elif name in ("WeightedCrossEntropyLoss", "FocalLoss", "SmoothedCrossEntropyLoss"):
         from . import losses as m
+    elif name == "ImprovedTrainStep":
+        from . import trainer as m
     elif name in ("FusedAdamW", "FusedAdam", "clip_grad_norm_"):
         from . import optim as m
     elif name in ("LogicRNNLSTM", "LogicCell", "create_model"):

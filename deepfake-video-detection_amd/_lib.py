@@ -82,6 +82,9 @@ _SIGS = {
                                 c_p, c_fpp]),
     "dfd_ce_forward": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_p, c_p]),
     "dfd_ce_backward": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_p, c_p, c_p]),
+    "dfd_loss_work_floats": (c_i64, [c_i, c_i]),
+    "dfd_loss_forward": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_d, c_d, c_i64, c_p, c_p]),
+    "dfd_loss_backward": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_d, c_d, c_i64, c_p, c_p, c_p]),
     "dfd_grad_norm": (c_i, [c_p, c_p, c_i64, c_f, c_p, c_p]),
     "dfd_collate_frames": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_i, c_p]),
     "dfd_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_d, c_d, c_i, c_d, c_i, c_p]),

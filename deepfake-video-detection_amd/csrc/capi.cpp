@@ -337,6 +337,43 @@ int dfd_ce_backward(void* stream, const float* logits, const int64_t* labels, co
   DFD_GUARD_END
 }
 
+static int loss_desc(dfd::LossDesc& d, int mode, int reduction, int B, int C, double gamma, double eps,
+                     int64_t ignore_index) {
+  if (!(eps >= 0.0 && eps < 1.0)) { dfd::set_error("classification loss: label_smoothing outside [0, 1)", __FILE__, __LINE__); return -1; }
+  d.mode = mode; d.reduction = reduction; d.B = B; d.C = C;
+  d.gamma = (float)gamma;
+  d.q_on = (float)(1.0 - eps);
+  d.q_off = mode == DFD_LOSS_FOCAL ? (C > 1 ? (float)(eps / (C - 1)) : 0.f) : (float)(eps / (C > 0 ? C : 1));
+  d.ignore = ignore_index;
+  return 0;
+}
+
+int64_t dfd_loss_work_floats(int B, int C) {
+  return B < 1 || C < 1 || C > dfd::kLossMaxClasses ? -1 : dfd::loss_work_floats(B, C);
+}
+
+int dfd_loss_forward(void* stream, int mode, int reduction, const float* logits, const int64_t* labels,
+                     const float* weight, int B, int C, double gamma, double label_smoothing, int64_t ignore_index,
+                     float* work, float* loss) {
+  DFD_GUARD_BEGIN
+  if (!logits || !labels || !work || !loss) { dfd::set_error("null argument", __FILE__, __LINE__); return -1; }
+  dfd::LossDesc d{};
+  if (loss_desc(d, mode, reduction, B, C, gamma, label_smoothing, ignore_index) != 0) return -1;
+  return dfd::loss_forward((hipStream_t)stream, d, logits, labels, weight, work, loss);
+  DFD_GUARD_END
+}
+
+int dfd_loss_backward(void* stream, int mode, int reduction, const int64_t* labels, const float* weight, int B, int C,
+                      double gamma, double label_smoothing, int64_t ignore_index, const float* work,
+                      const float* grad_out, float* dlogits) {
+  DFD_GUARD_BEGIN
+  if (!labels || !work || !grad_out || !dlogits) { dfd::set_error("null argument", __FILE__, __LINE__); return -1; }
+  dfd::LossDesc d{};
+  if (loss_desc(d, mode, reduction, B, C, gamma, label_smoothing, ignore_index) != 0) return -1;
+  return dfd::loss_backward((hipStream_t)stream, d, labels, weight, work, grad_out, dlogits);
+  DFD_GUARD_END
+}
+
 int dfd_grad_norm(void* stream, const float* grads, int64_t n, float max_norm, void* scratch, float* out2) {
   DFD_GUARD_BEGIN
   return dfd::grad_norm((hipStream_t)stream, grads, n, max_norm, (double*)scratch, 1024, out2);

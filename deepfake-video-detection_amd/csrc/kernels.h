@@ -496,6 +496,25 @@ int launch_stem_wgrad(hipStream_t s, const StemGeom& g, const void* x, const T* 
 int launch_collate_gather(hipStream_t s, const uint8_t* src, const int64_t* sel, int64_t nsel, int64_t frame_bytes,
                           bool f32, void* out);
 
+// ---------------- focal / label-smoothed classification losses: k_loss.hip ----------------
+// FocalLoss and nn.CrossEntropyLoss(weight, label_smoothing) of src/train_improved.py:29-78,136-150.
+// q_on = 1 - eps; q_off = eps / (C - 1) (focal; 0 if C == 1) or eps / C (ce).  work: loss_work_floats(B, C)
+// floats, written by the forward (row softmax, per-row terms, the mean's divisor) and read by the backward.
+// out: () for mean / sum, (B) for none.  gout: the upstream gradient on the device, () or (B) alike.
+enum { LOSS_FOCAL = 0, LOSS_CE = 1 };
+enum { LOSS_REDUCE_NONE = 0, LOSS_REDUCE_MEAN = 1, LOSS_REDUCE_SUM = 2 };
+constexpr int kLossMaxClasses = 1024;
+struct LossDesc {
+  int mode, reduction, B, C;
+  float gamma, q_on, q_off;
+  int64_t ignore;  // ce only
+};
+int64_t loss_work_floats(int B, int C);
+int loss_forward(hipStream_t s, const LossDesc& d, const float* z, const int64_t* y, const float* w, float* work,
+                 float* out);
+int loss_backward(hipStream_t s, const LossDesc& d, const int64_t* y, const float* w, const float* work,
+                  const float* gout, float* dz);
+
 // ---------------- misc: k_misc.hip ----------------
 struct CastSeg {
   int64_t src, dst;  // element offsets

@@ -8,6 +8,8 @@ implementation for shape propagation, and autograd where the op is differentiabl
   dfd::b0_trunk_forward / dfd::b0_trunk_backward   the EfficientNet-B0 trunk plan (timm conv_stem ..
                                                    global_pool, src/pretrained_detector.py:116)
   dfd::weighted_cross_entropy (+ _backward)        nn.CrossEntropyLoss(weight) (ensemble_trainer.py:358)
+  dfd::classification_loss (+ _backward)           FocalLoss / nn.CrossEntropyLoss(weight, label_smoothing)
+                                                   (train_improved.py:29-78, 136-150)
   dfd::grad_norm, dfd::adam_step                   clip_grad_norm_(1.0) + AdamW (ensemble_trainer.py:196-200)
   dfd::grad_norm_scaled, dfd::adam_step_scaled,    the same under dynamic loss scaling (fp16 training:
   dfd::loss_scale_update                           GradScaler unscale_ / step / update, on the device)
@@ -139,6 +141,90 @@ def _ce_backward(ctx, gloss, _gwsum):
 weighted_cross_entropy.register_autograd(_ce_backward, setup_context=_ce_setup)
 
 
+# ---------------------------------------------------------------- focal / label-smoothed losses
+LOSS_MODES = {"focal": 0, "ce": 1}
+LOSS_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+
+def _loss_codes(mode: str, reduction: str):
+    if mode not in LOSS_MODES or reduction not in LOSS_REDUCTIONS:
+        raise _lib.DFDError(f"classification_loss: unknown mode {mode!r} or reduction {reduction!r}")
+    return LOSS_MODES[mode], LOSS_REDUCTIONS[reduction]
+
+
+def _loss_work_floats(B: int, C: int) -> int:
+    n = int(_lib.load().dfd_loss_work_floats(B, C))
+    if n < 0:
+        raise _lib.DFDError(f"classification_loss: needs B >= 1 and 1 <= C <= 1024 (got B = {B}, C = {C})")
+    return n
+
+
+@torch.library.custom_op("dfd::classification_loss", mutates_args=(), device_types="cuda")
+def classification_loss(logits: Tensor, target: Tensor, weight: Optional[Tensor], mode: str, reduction: str,
+                        gamma: float, label_smoothing: float, ignore_index: int) -> Tuple[Tensor, Tensor]:
+    """mode 'focal': FocalLoss(gamma, weight, label_smoothing); 'ce': cross_entropy(weight, label_smoothing,
+    ignore_index).  -> (loss: () for 'mean' / 'sum', (B,) for 'none'; the backward's workspace)."""
+    lib = _lib.load()
+    m, r = _loss_codes(mode, reduction)
+    logits = logits.contiguous().float()
+    target = target.contiguous().long()
+    weight = None if weight is None else weight.contiguous().float()
+    B, C = logits.shape
+    work = torch.empty(_loss_work_floats(B, C), dtype=torch.float32, device=logits.device)
+    loss = torch.empty((B,) if reduction == "none" else (), dtype=torch.float32, device=logits.device)
+    _lib.check(lib.dfd_loss_forward(_lib.stream_of(logits.device), m, r, logits.data_ptr(), target.data_ptr(),
+                                    _lib.ptr(weight), B, C, float(gamma), float(label_smoothing), int(ignore_index),
+                                    work.data_ptr(), loss.data_ptr()))
+    return loss, work
+
+
+@classification_loss.register_fake
+def _(logits, target, weight, mode, reduction, gamma, label_smoothing, ignore_index):
+    B, C = logits.shape
+    return (logits.new_empty((B,) if reduction == "none" else (), dtype=torch.float32),
+            logits.new_empty(_loss_work_floats(B, C), dtype=torch.float32))
+
+
+@torch.library.custom_op("dfd::classification_loss_backward", mutates_args=(), device_types="cuda")
+def classification_loss_backward(grad: Tensor, target: Tensor, weight: Optional[Tensor], work: Tensor,
+                                 num_classes: int, mode: str, reduction: str, gamma: float, label_smoothing: float,
+                                 ignore_index: int) -> Tensor:
+    """grad: the upstream gradient, () or (B,) like the loss; read on the device.  -> dlogits (B, C) fp32."""
+    lib = _lib.load()
+    m, r = _loss_codes(mode, reduction)
+    target = target.contiguous().long()
+    weight = None if weight is None else weight.contiguous().float()
+    B, C = target.shape[0], int(num_classes)
+    if work.numel() != _loss_work_floats(B, C) or grad.numel() != (B if reduction == "none" else 1):
+        raise _lib.DFDError("classification_loss_backward: workspace or gradient of another shape")
+    g = grad.contiguous().float()
+    d = torch.empty(B, C, dtype=torch.float32, device=work.device)
+    _lib.check(lib.dfd_loss_backward(_lib.stream_of(work.device), m, r, target.data_ptr(), _lib.ptr(weight), B, C,
+                                     float(gamma), float(label_smoothing), int(ignore_index), work.data_ptr(),
+                                     g.data_ptr(), d.data_ptr()))
+    return d
+
+
+@classification_loss_backward.register_fake
+def _(grad, target, weight, work, num_classes, mode, reduction, gamma, label_smoothing, ignore_index):
+    return work.new_empty(target.shape[0], num_classes, dtype=torch.float32)
+
+
+def _loss_setup(ctx, inputs, output):
+    logits, target, weight, *ctx.args = inputs
+    ctx.save_for_backward(target, output[1])
+    ctx.weight, ctx.num_classes, ctx.dtype = weight, logits.shape[1], logits.dtype
+
+
+def _loss_backward(ctx, gloss, _gwork):
+    target, work = ctx.saved_tensors
+    d = torch.ops.dfd.classification_loss_backward(gloss, target, ctx.weight, work, ctx.num_classes, *ctx.args)
+    return (d.to(ctx.dtype), None, None, None, None, None, None, None)
+
+
+classification_loss.register_autograd(_loss_backward, setup_context=_loss_setup)
+
+
 # ---------------------------------------------------------------- optimizer
 # scratch: the kernel's fixed-order partial sums (written); out: [norm, clip coefficient]
 @torch.library.custom_op("dfd::grad_norm", mutates_args=("scratch", "out"), device_types="cuda")
@@ -241,3 +327,5 @@ def _(src, sel, frame_shape, to_float):
 
 OPS = ("b0_trunk_forward", "b0_trunk_backward", "weighted_cross_entropy", "weighted_cross_entropy_backward",
        "grad_norm", "adam_step", "grad_norm_scaled", "adam_step_scaled", "loss_scale_update", "collate_frames")
+# the losses of the ViT+GCN trainer (losses.FocalLoss / SmoothedCrossEntropyLoss)
+LOSS_OPS = ("classification_loss", "classification_loss_backward")

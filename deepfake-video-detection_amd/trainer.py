@@ -17,13 +17,23 @@ mean.  BatchNorm statistics stay local per rank (the reference has no SyncBN).
 With the fp16 trunk (``compute_dtype="fp16"``) the step scales the loss by a ``DynamicLossScaler``
 before backward (fp16 activation gradients would underflow) and the fused optimizer unscales, skips
 non-finite steps and updates the scale on the device (``torch.amp.GradScaler`` semantics, no sync).
+
+``ImprovedTrainStep`` is the step of the reference's ``ImprovedTrainer`` (``src/train_improved.py:104-232``),
+the trainer of ``DeepfakeModel`` (ViT-B/16 + SimpleGCN)::
+
+    optimizer.zero_grad(); logits = model(frames, A_norm); loss = criterion(logits, labels)
+    loss.backward(); clip_grad_norm_(model.parameters(), 1.0); optimizer.step()
+
+with ``FocalLoss`` or the label-smoothed cross entropy on HIP, AdamW under ``CosineAnnealingLR`` stepped once
+per epoch.  Its per-epoch metrics, ``ReduceLROnPlateau``, early stopping and checkpoint naming are host
+bookkeeping on scalars and stay with the caller.
 """
 from __future__ import annotations
 
 import torch
 import torch.distributed as dist
 
-from .losses import WeightedCrossEntropyLoss
+from .losses import FocalLoss, SmoothedCrossEntropyLoss, WeightedCrossEntropyLoss
 from .optim import DynamicLossScaler, FusedAdam, FusedAdamW
 
 
@@ -131,3 +141,47 @@ class DataParallelTrainer(TrainStep):
         for w in self._works:
             w.wait()
         self._works.clear()
+
+
+class ImprovedTrainStep:
+    """``ImprovedTrainer(model, device, config)``'s optimisation step.  ``config`` keys, as in the reference:
+    ``learning_rate``, ``weight_decay``, ``max_epochs``, ``class_weights`` (required), ``loss`` (``'focal'`` or
+    ``'cross_entropy'``, the default), ``label_smoothing`` (0), ``focal_gamma`` (2).  ``model`` is on its HIP
+    device already.  Nothing in a step synchronises with the host."""
+
+    def __init__(self, model, config):
+        self.model = model
+        self.config = config
+        lr = float(config["learning_rate"])
+        smoothing = float(config.get("label_smoothing", 0.0))
+        weight = torch.as_tensor(config["class_weights"], dtype=torch.float32)
+        loss_name = config.get("loss", "cross_entropy")
+        if loss_name == "focal":
+            self.criterion = FocalLoss(gamma=float(config.get("focal_gamma", 2.0)), weight=weight,
+                                       label_smoothing=smoothing)
+        elif loss_name == "cross_entropy":
+            self.criterion = SmoothedCrossEntropyLoss(weight=weight, label_smoothing=smoothing)
+        else:
+            raise ValueError(f"config['loss'] must be 'focal' or 'cross_entropy' (got {loss_name!r})")
+        if hasattr(model, "ensure_flat"):
+            model.ensure_flat()
+        self.optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=float(config["weight_decay"]),
+                                    betas=(0.9, 0.999), max_grad_norm=1.0)
+        self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=int(config["max_epochs"]),
+                                                                    eta_min=lr * 0.01)
+
+    def forward_backward(self, frames, A_norm, labels):
+        self.optimizer.zero_grad(set_to_none=True)
+        logits = self.model(frames, A_norm)
+        loss = self.criterion(logits, labels)
+        loss.backward()
+        return loss, logits
+
+    def __call__(self, frames, A_norm, labels):
+        loss, logits = self.forward_backward(frames, A_norm, labels)
+        self.optimizer.step()
+        return loss, logits
+
+    def scheduler_step(self) -> None:
+        """once per epoch, after its steps (``self.scheduler.step()`` in the reference's epoch loop)"""
+        self.scheduler.step()

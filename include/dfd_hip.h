@@ -226,6 +226,32 @@ DFD_API int dfd_ce_backward(void* stream, const float* logits, const int64_t* la
                             int NC, int64_t ignore_index, const float* wsum, const float* grad_out,
                             float* dlogits);
 
+/* ---- focal / label-smoothed classification losses ----------------------------------------
+ * Replaces the two criteria of ImprovedTrainer (src/train_improved.py): FocalLoss(gamma, weight,
+ * label_smoothing) (:29-78, mode DFD_LOSS_FOCAL; `mean` is the plain mean over the B rows, there is no
+ * ignore_index) and nn.CrossEntropyLoss(weight, label_smoothing) (:136-150, mode DFD_LOSS_CE; torch's
+ * formula: `mean` divides by the sum of weight[label] over the rows that are not ignore_index, the
+ * smoothing term weights every class).  logits (B, C) fp32, 1 <= C <= 1024, labels (B) int64, weight
+ * (C) fp32 or NULL.  loss: one float for DFD_REDUCE_MEAN / _SUM, B floats for DFD_REDUCE_NONE.  work:
+ * dfd_loss_work_floats(B, C) floats, written by the forward and read by the backward of the same call
+ * arguments.  grad_out: the upstream gradient in device memory, one float or B floats alike (never read
+ * by the host).  The result is the same bits on every run (fixed-order sums, no atomics).  A row
+ * whose label is outside [0, C) (and is not ignore_index in CE mode) reads nothing through the label,
+ * gets a NaN loss and a zero gradient.  0 < gamma < 1 with pt rounding to 1 is undefined (inf or NaN
+ * gradients), as in the reference. */
+#define DFD_LOSS_FOCAL 0
+#define DFD_LOSS_CE 1
+#define DFD_REDUCE_NONE 0
+#define DFD_REDUCE_MEAN 1
+#define DFD_REDUCE_SUM 2
+DFD_API int64_t dfd_loss_work_floats(int B, int C);
+DFD_API int dfd_loss_forward(void* stream, int mode, int reduction, const float* logits, const int64_t* labels,
+                             const float* weight, int B, int C, double gamma, double label_smoothing,
+                             int64_t ignore_index, float* work, float* loss);
+DFD_API int dfd_loss_backward(void* stream, int mode, int reduction, const int64_t* labels, const float* weight,
+                              int B, int C, double gamma, double label_smoothing, int64_t ignore_index,
+                              const float* work, const float* grad_out, float* dlogits);
+
 /* ---- input pipeline ----------------------------------------------------------------------
  * Replaces the frame gather of collate_batch_cnn_lstm / collate_batch (src/train.py:38-61,
  * 62-100): out[s] = src[sel[s]] for s < nsel, frames of frame_bytes uint8 each (sel[s] < 0: an
