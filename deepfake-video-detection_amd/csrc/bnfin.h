@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "bn_common.h"
 
 namespace dfd {
 
@@ -87,21 +88,17 @@ __device__ __forceinline__ void bn_fin_wg(const BnFwdFin& f, int C, int c0, int 
     const double m = ts / cnt;
     double var = tq / cnt - m * m;
     if (var < 0.0) var = 0.0;
-    const float mu = (float)m, is = (float)(1.0 / sqrt(var + (double)f.eps));
-    const float g = f.gamma[c];
-    const float scv = g * is, shv = f.beta[c] - mu * scv;
-    sc[tid] = scv;
-    sh[tid] = shv;
+    const bool run = writer && f.run_mean;
+    const BnFwdCoef o = bn_fwd_epilogue(m, var, f.count, f.gamma[c], f.beta[c], run ? f.run_mean[c] : 0.f,
+                                        run ? f.run_var[c] : 0.f, f.momentum, f.eps, 1, run);
+    sc[tid] = o.sc;
+    sh[tid] = o.sh;
     if (writer) {
-      f.mean[c] = mu;
-      f.invstd[c] = is;
-      f.scale[c] = scv;
-      f.shift[c] = shv;
-      if (f.run_mean) {
-        const double unb = f.count > 1 ? var * cnt / (cnt - 1.0) : var;
-        f.run_mean[c] = (float)((1.0 - f.momentum) * f.run_mean[c] + f.momentum * m);
-        f.run_var[c] = (float)((1.0 - f.momentum) * f.run_var[c] + f.momentum * unb);
-      }
+      f.mean[c] = o.mu;
+      f.invstd[c] = o.is;
+      f.scale[c] = o.sc;
+      f.shift[c] = o.sh;
+      if (run) { f.run_mean[c] = o.rm; f.run_var[c] = o.rv; }
     }
   }
   __syncthreads();

@@ -142,15 +142,14 @@ __device__ void mb7_bn_finalize(const Mb7Bn& bn, const float* __restrict__ part,
       const double m = s / (double)count;
       double var = q / (double)count - m * m;
       if (var < 0.0) var = 0.0;
-      const float is = (float)(1.0 / sqrt(var + (double)eps));
-      const double unb = count > 1 ? var * (double)count / (double)(count - 1) : var;
-      bn.run_mean[c] = (float)((1.0 - momentum) * bn.run_mean[c] + momentum * m);
-      bn.run_var[c] = (float)((1.0 - momentum) * bn.run_var[c] + momentum * unb);
-      const float sc = bn.gamma[c] * is;
-      bn.mean[c] = (float)m;
-      bn.invstd[c] = is;
-      bn.scale[c] = sc;
-      bn.shift[c] = bn.beta[c] - (float)m * sc;
+      const BnFwdCoef o = bn_fwd_epilogue(m, var, count, bn.gamma[c], bn.beta[c], bn.run_mean[c], bn.run_var[c],
+                                          momentum, eps, 1, true);
+      bn.run_mean[c] = o.rm;
+      bn.run_var[c] = o.rv;
+      bn.mean[c] = o.mu;
+      bn.invstd[c] = o.is;
+      bn.scale[c] = o.sc;
+      bn.shift[c] = o.sh;
     }
   }
 }

@@ -2,7 +2,7 @@
 // high-resolution blocks, bf16 (src/pretrained_detector.py:116 runs the timm blocks).
 //
 // The BN after conv_pw has the input gradient ge1 = k1*g + k2*y1 + k3 and y1 = x . W^T, so by
-// linearity (bn_fold_pw, k_bn.hip) the conv's gradients need only g and the block input x:
+// linearity (bn_fold_pw, k_frame.hip) the conv's gradients need only g and the block input x:
 //   dX  = g . W1t^T + x . Q^T + bv (+ the block's skip gradient)     W1t = diag(k1) W (as [cin][mid])
 //   dW  = diag(k1) T + diag(k2) W G + k3 cs^T                        (pw_wgrad_bn_combine)
 //   T   = g^T x   [mid][cin],   G = x^T x   [cin][cin],   cs = 1^T x   [cin]

@@ -4,7 +4,7 @@
 //
 //   ge2[m][k]        = sum_n gs[m][n] W[n][k]                                   data gradient (stored)
 //   dW[n][k]        += sum_m gs[m][n] act[m][k],  act = silu(y2*sc+sh) * gate[f][k]   weight gradient
-//   part[q][h][f][k] = per-frame sums D, P1..P4 of (ge2, y2)                    (k_bn.hip FR_SEBN)
+//   part[q][h][f][k] = per-frame sums D, P1..P4 of (ge2, y2)                 (k_frame.hip FR_SEBN)
 //
 // gs = dL/d(y3) after the BN3 backward [M][N = cout], y2 = the pre-BN2 depthwise output [M][K = mid].
 // The unfused path ran three launches over the expanded tensor -- the dgrad GEMM (writes ge2), the

@@ -93,7 +93,7 @@ int launch_pw_fold_bwd(hipStream_t s, const E* g, const E* x, const E* r, const 
   X(TK_VG_XP, "vg_xp", DFD_VG_XP_DEFAULT)                                                                              \
   /* BN finalizes in the producers' last-arriving workgroups (tail.h) instead of their own launches (bit 0: the       \
      SE-backward chain's BN2 finalize); bit 1: the SE excitation's first product split over its channel slices        \
-     (k_bn.hip SeSplit); bit 2: BN backward finalize inside the apply pass (bn_bwd_apply_fin) where the producer      \
+     (k_se.hip SeSplit); bit 2: BN backward finalize inside the apply pass (bn_bwd_apply_fin) where the producer      \
      wrote <= 256 stat rows; bit 3: forward BN finalize inside the consumer (depthwise forward, SE squeeze, global    \
      average pool) where the producer wrote <= 128 rows (kBnFinRowsMax) */                                             \
   X(TK_TAIL_FIN, "tail_fin", DFD_TAIL_FIN_DEFAULT)                                                                     \
@@ -289,7 +289,7 @@ int try_dw_fwd1(hipStream_t s, const DwGeom& g, const T* X, const float* w, T* Y
                 int* stat_rows, const BnFwdFin* fin = nullptr);
 bool dw_fwd1_enabled();
 
-// ---------------- BatchNorm / SE / pooling: k_bn.hip ----------------
+// ---------------- BatchNorm: k_bn.hip; per-frame reductions / pooling: k_frame.hip; SE: k_se.hip ----------------
 // finalize training stats: mean/invstd/scale/shift + running update (momentum); eval: from running
 // chan_rows > 0: stats rows are centred (sum, M2) partials of consecutive chan_rows-row tiles
 // (conv_forward's epilogue: kConvStatRows), merged in fp64 (Chan); 0: plain (sum, sum of squares)
@@ -346,13 +346,13 @@ template <typename T>
 int launch_bn_bwd_apply_fin(hipStream_t s, const BnBwdIn& in, const T* Y, int64_t M, int C, const float* stats, int rows,
                             int64_t count, const float* gamma, const float* mean, const float* invstd, bool training,
                             float* dgamma, float* dbeta, bool accumulate, float* coef, T* dY);
-// SE squeeze partials: part[h][f][c] = sum over pixel chunk h of pro(Y)   (pro = BN+SiLU), h < *hsplit
+// SE squeeze partials (k_frame.hip): part[h][f][c] = sum over pixel chunk h of pro(Y)   (pro = BN+SiLU), h < *hsplit
 // s_out: optional materialised silu(bn(Y)); fin: the BN's finalize (inside the launch where the stat rows
 // are few, else its own launch first)
 template <typename T>
 int launch_se_squeeze(hipStream_t s, const T* Y, const Pro& pro, int frames, int HW, int C, float* part,
                       int64_t part_cap, int* hsplit, T* s_out, const BnFwdFin* fin = nullptr);
-// scratch of the split SE excitation (k_bn.hip se_chain_kernel SPLIT): zeroed counters (2 per 16-frame
+// scratch of the split SE excitation (k_se.hip se_chain_kernel SPLIT): zeroed counters (2 per 16-frame
 // tile) and partial first products; nullptr (or too small) runs the unsplit form
 struct SeScratch {
   unsigned* bar;
@@ -364,14 +364,10 @@ struct SeScratch {
   int* abort_dev = nullptr;
   int* abort_host = nullptr;
 };
-// SE excitation: sq = inv_hw * sum_h part (stored) ; r = silu(Wr sq + br) ; gate = sigmoid(We r + be) ; saves rpre
+// SE excitation (k_se.hip): sq = inv_hw * sum_h part (stored) ; r = silu(Wr sq + br) ; gate = sigmoid(We r + be) ; saves rpre
 int launch_se_fc_fwd(hipStream_t s, const float* part, int hsplit, float inv_hw, float* sq, const float* wr,
                      const float* br, const float* we, const float* be, int frames, int C, int rd, float* rpre,
                      float* gate, const SeScratch* sc = nullptr);
-// SE backward reduce: dgate[f][c] = sum_hw dZ * pro(Y)   (pro = BN+SiLU, no gate)
-template <typename T>
-int launch_se_bwd_reduce(hipStream_t s, const T* dZ, const T* Y, const Pro& pro, int frames, int HW, int C,
-                         float* part, int64_t part_cap, float* dgate);
 // SE FC backward: from dgate -> dsq (written, scaled by 1/HW into bc), grads of wr,br,we,be.
 // tmp_de: frames*C floats; tmp_dr: 2*frames*rd floats
 // (de = dgate g (1-g) from the q = 0 partials of launch_se_bn_bwd_reduce, stored to `de`)
@@ -397,7 +393,7 @@ int launch_se_fc_bwd(hipStream_t s, const float* part, int hsplit, const float* 
                      MfmaGemm* defer2 = nullptr, const BnFramesFin* bnf = nullptr, const SeScratch* sc = nullptr);
 // SE + BN(+SiLU) backward sums in one pass over (dZ, Y): per-frame partials part[5][hsplit][frames][C] -- q = 0
 // the SE gate gradient (added by launch_se_fc_bwd), q = 1..4 the sums bn_bwd_finalize_frames combines with the
-// gate and bc (k_bn.hip)
+// gate and bc (k_frame.hip)
 template <typename T>
 int launch_se_bn_bwd_reduce(hipStream_t s, const T* dZ, const T* Y, const float* scale, const float* shift,
                             const float* mean, const float* invstd, int frames, int HW, int C, float* part,
@@ -406,7 +402,7 @@ int launch_bn_bwd_finalize_frames(hipStream_t s, float* part, int hsplit, const 
                                   int frames, int C, int64_t count, const float* gamma, const float* mean,
                                   const float* invstd, bool training, float* dgamma, float* dbeta, bool accumulate,
                                   float* coef);
-// conv_pw backward through its BN (no activation), by linearity (k_bn.hip): fold the BN-backward
+// conv_pw backward through its BN (no activation), by linearity (k_frame.hip): fold the BN-backward
 // coefficients coef = [k1; k2; k3] into the dgrad operands, combine the weight-gradient terms
 template <typename T>
 int launch_bn_fold_pw(hipStream_t s, const float* W, const float* coef, int mid, int cin, T* w1t, T* q, float* bv);
@@ -442,10 +438,11 @@ int launch_mfma_small_gemm(hipStream_t s, const float* A, int64_t sam, int64_t s
                            int64_t sbn, float* C, int64_t ldc, int M, int N, int K, const float* bias,
                            const float* dsilu_pre, float* asum, bool accumulate, uint64_t seed, uint32_t stream,
                            float p, int64_t drop_ld);
-// head global average pool: feat[f][c] = mean_hw silu(Y*scale+shift)
+// head global average pool (k_frame.hip): feat[f][c] = mean_hw silu(Y*scale+shift)
 template <typename T>
 int launch_gap(hipStream_t s, const T* Y, const Pro& pro, int frames, int HW, int C, float* feat,
                const BnFwdFin* fin = nullptr);
+// ---------------- slab reducer: k_reduce.hip ----------------
 // sum `splits` slabs of n floats into out (= or +=)
 // Deferred weight-gradient reductions: while a SlabDefer is active on the calling thread, slab
 // reductions on `stream` whose output lies inside [lo, hi) (the gradient buffer) are queued and

@@ -228,7 +228,7 @@ int plan_build(Plan& p, int frames, int H, int W, int dtype) {
   p.o_gram = alloc(maxCin * maxCin * 4);
   p.o_cs = alloc(maxCin * 4);
   p.o_bar = alloc(kBarBytes);
-  // last-arrival / slice-barrier counters (tail.h, k_bn.hip se_chain): in the per-call workspace, so
+  // last-arrival / slice-barrier counters (tail.h, k_se.hip se_chain): in the per-call workspace, so
   // concurrent calls of one plan on different streams (the app's worker threads) never share them;
   // zeroed at the start of every forward, and every use leaves them zero again
   p.o_ctr = alloc(kCtrSlots * sizeof(unsigned));
@@ -844,7 +844,7 @@ struct Backward {
   // ge1 = k1*g + k2*y1 + k3 is never materialised; by linearity (y1 = x . W^T) the gradients need only g
   // (in ge1) and the block input x:
   //   dX = g . diag(k1)W + x . W^T diag(k2) W + W^T k3 (+ skip);  dW = diag(k1) g^T x +
-  //   diag(k2) W x^T x + k3 1^T x   (bn_fold_pw, k_bn.hip)
+  //   diag(k2) W x^T x + k3 1^T x   (bn_fold_pw, k_frame.hip)
   int expansion_fold(const Block& b, const T* xin, const T* resid, T* gxo, int nrows) {
     const int64_t Min = rows_in(b);
     DFD_TRY(bn_finalize(b.bn1, nrows, Min, r.f(p.o_coef1)));

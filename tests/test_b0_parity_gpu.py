@@ -87,6 +87,26 @@ def _check_grads(det, g, rtol_norm=1e-3, atol_head=1e-5, rtol_head=1e-3):
 
 
 def test_detector_train_golden_fp32(cuda, golden_dir, kernel_paths):
+    _train_golden_fp32(cuda, golden_dir)
+
+
+@pytest.mark.parametrize("tail_fin", [14, 15])
+def test_detector_train_golden_fp32_frames_finalize(cuda, golden_dir, tail_fin):
+    """The SE-backward BN2 finalize as its own launch (knob tail_fin bit 0 off: sum_parts4 +
+    bn_bwd_finalize_frames_kernel, k_frame.hip) next to the one inside the excitation launch (bit 0 on,
+    the default: se_chain_kernel<false, true>, k_se.hip), each against the fp32 golden step with the
+    bounds of the kernel-selection knobs above; the other bits stay at their default."""
+    from deepfake_amd import backbone
+    prev = dict(backbone.DEFAULT_TUNING)
+    backbone.DEFAULT_TUNING["tail_fin"] = tail_fin
+    try:
+        _train_golden_fp32(cuda, golden_dir)
+    finally:
+        backbone.DEFAULT_TUNING.clear()
+        backbone.DEFAULT_TUNING.update(prev)
+
+
+def _train_golden_fp32(cuda, golden_dir):
     g = np.load(os.path.join(golden_dir, "b0_train_64.npz"))
     det = _det(int(g["seed"]), "fp32", dropout=0.0, cuda=cuda).train()
     x = torch.from_numpy(g["x"]).to(cuda)

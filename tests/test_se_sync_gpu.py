@@ -1,7 +1,7 @@
 """The split SE excitation's slice barrier under device contention.
 
 At 256 frames the SE excitation of the 1152-channel blocks splits its first product over 5 channel
-slices that meet at a software barrier (``k_bn.hip`` se_chain_kernel, ``tail.h`` group_sync).  The
+slices that meet at a software barrier (``k_se.hip`` se_chain_kernel, ``tail.h`` group_sync).  The
 launcher turns the split on only when the grid fits the device at once, but another stream's kernels
 (the data-parallel trainer's RCCL all-reduce runs on a side stream during backward) can
 hold the CUs the grid needs.  The barrier is bounded (2 s of wall clock); a group that times out
