@@ -1,6 +1,10 @@
-// Shared helpers of the channel-pair depthwise kernels (k_dw_fwd1.hip, k_dw_bwd1.hip): a lane owns
-// two adjacent channels, held as a packed fp32 pair (v_pk_fma_f32 math), loaded from NHWC global
-// memory as one dword (bf16) or dwordx2 (fp32).
+// The shared skeleton of the channel-pair depthwise kernels (k_dw_fwd1.hip, k_dw_bwd1.hip,
+// k_dw_bwd2.hip): a lane owns two adjacent channels, held as a packed fp32 pair (v_pk_fma_f32 math),
+// loaded from NHWC global memory as one dword (bf16 / f16) or dwordx2 (fp32).  Below the pair
+// primitives: the LDS fills of the weights and the backward constants, the tile decode, the
+// BN2-backward pair math of the two backward kernels, and the host's grid rule and launch tail.
+// What shapes a kernel's schedule (row fences, register pins, prefetch) stays in the kernel; so do
+// the sites where a shared helper changed a kernel's register counts (DESIGN.md lists them).
 #pragma once
 #include "dw_common.h"
 
@@ -84,6 +88,75 @@ __device__ __forceinline__ void lane_sum4(v2f& v) {
   v.y += __shfl_xor(v.y, 16, 64);
   v.x += __shfl_xor(v.x, 32, 64);
   v.y += __shfl_xor(v.y, 32, 64);
+}
+
+// ---- LDS fills (256 threads; channel group c0 .. c0+31 of C) ----
+// the group's depthwise weights as [tap][ch]
+template <int K>
+__device__ __forceinline__ void dw1_fill_wts(float* wts, const float* w, int c0, int C) {
+  for (int i = threadIdx.x; i < K * K * DCG; i += 256) {
+    const int tap = i / DCG, cl = i - tap * DCG;
+    wts[i] = (c0 + cl < C) ? w[(int64_t)(c0 + cl) * K * K + tap] : 0.f;
+  }
+}
+// the backward kernels' per-channel constants: sc2 sh2 k1 k2 k3 | sc1 sh1 mean1 invstd1
+__device__ __forceinline__ void dw1_fill_bwd_cst(float (&cst)[9][DCG], const Dw1Bn2& b2, const BnBwdIn& bn1, int c0,
+                                                 int C) {
+  for (int i = threadIdx.x; i < 9 * DCG; i += 256) {
+    const int k = i / DCG, cl = i - k * DCG, c = c0 + cl;
+    const bool ok = c < C;
+    float v = 0.f;
+    switch (k) {
+      case 0: v = ok ? b2.sc[c] : 0.f; break;
+      case 1: v = ok ? b2.sh[c] : 0.f; break;
+      case 2: v = ok ? b2.coef[c] : 0.f; break;
+      case 3: v = ok ? b2.coef[C + c] : 0.f; break;
+      case 4: v = ok ? b2.coef[2 * C + c] : 0.f; break;
+      case 5: v = ok ? bn1.scale[c] : 1.f; break;
+      case 6: v = ok ? bn1.shift[c] : 0.f; break;
+      case 7: v = ok ? bn1.mean[c] : 0.f; break;
+      default: v = ok ? bn1.invstd[c] : 1.f; break;
+    }
+    cst[k][cl] = v;
+  }
+}
+// ---- staging ----
+// tile t of a launch -> its first frame and its origin in the map (tpf tiles per frame; a tile is FR
+// whole frames, or TH x TW of one)
+struct Dw1Tile {
+  int f, iy0, ix0;
+};
+__device__ __forceinline__ Dw1Tile dw1_tile(int t, int tpf, int tiles_x, int FR, int TH, int TW) {
+  const int f = (t / tpf) * FR, r = t - (t / tpf) * tpf, ty = r / tiles_x;
+  return {f, ty * TH, (r - ty * tiles_x) * TW};
+}
+// BN2(+SiLU, SE gate) backward of one channel pair (channels cq, cq+1 of the group) of a staged pixel:
+// dY = k1*g2 + k2*y + k3, g2 = (z*gate + bc) * silu'(y*sc2 + sh2), rounded to T
+template <typename T>
+__device__ __forceinline__ v2f bn2_bwd_pair(v2f z, v2f y, const float (&cst)[9][DCG], const float (&gb)[2][DCG],
+                                            int cq) {
+  const v2f tz = fma2(y, lds2(&cst[0][cq]), lds2(&cst[1][cq]));
+  const v2f sg = sigmoid2(tz);
+  const v2f ds = sg * fma2(tz, 1.0f - sg, v2f{1.f, 1.f});
+  const v2f g2 = fma2(z, lds2(&gb[0][cq]), lds2(&gb[1][cq])) * ds;
+  return round2(fma2(lds2(&cst[2][cq]), g2, fma2(lds2(&cst[3][cq]), y, lds2(&cst[4][cq]))), (T*)nullptr);
+}
+
+// ---- host: grid and launch ----
+// One workgroup row per co-resident set of the `groups` channel groups, at most one per tile, per slab
+// row (per floats each; per = 0: no weight gradient) and per BN-stat partial row of the plan.  Launches
+// KERN(args...) on rows * groups workgroups, reports the rows and sums the slab rows into dW
+template <auto KERN, typename... A>
+static int dw1_launch(hipStream_t s, int ntiles, int groups, int* stat_rows, float* slab, int64_t slab_cap, int64_t per,
+                      float* dW, bool accumulate, const A&... args) {
+  const int resident = resident_wgs<KERN, 256>();
+  int64_t rows = std::min<int64_t>(ntiles, std::max(1, resident / groups));
+  if (per > 0) rows = std::max<int64_t>(1, std::min<int64_t>(rows, slab_cap / per));
+  rows = std::min<int64_t>(rows, 1024);  // the plan's BN-stat partial rows
+  hipLaunchKernelGGL(KERN, dim3((unsigned)(rows * groups)), dim3(256), 0, s, args...);
+  DFD_HIP_CHECK(hipGetLastError());
+  if (stat_rows) *stat_rows = (int)rows;
+  return per > 0 ? launch_reduce_slabs(s, slab, (int)rows, per, dW, accumulate) : 0;
 }
 
 }  // namespace dfd

@@ -33,13 +33,6 @@ namespace dfd {
 
 // 1: fused (default); 0: the two kernels (dgrad, wgrad)
 bool dw_bwd_fused_enabled() { return tune(TK_DW_BWD_FUSED) != 0; }
-// 1: the stride-1 blocks take dw_bwd1_kernel (k_dw_bwd1.hip) with both BN backward passes fused
-
-bool dw_bwd1_enabled() {
-  return dw_bwd_fused_enabled() && tune(TK_DW_BWD1) != 0;
-}
-// 1: the stride-1 forward takes dw_fwd1_kernel (k_dw_fwd1.hip, channel pairs)
-bool dw_fwd1_enabled() { return tune(TK_DW_FWD1) != 0; }
 
 template <int TH, int TW, int K, int S, int VW>
 struct DwB {

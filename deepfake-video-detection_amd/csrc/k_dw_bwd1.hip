@@ -63,27 +63,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && K == 3 && !PF && RB == 1) ?
   const int bid = xcd ? xcd_swizzle((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
   const int grp = bid % groups;
   const int c0 = grp * DCG, C = g.C;
-  for (int i = tid; i < K * K * DCG; i += 256) {
-    const int tap = i / DCG, cl = i - tap * DCG;
-    wts[i] = (c0 + cl < C) ? w[(int64_t)(c0 + cl) * K * K + tap] : 0.f;
-  }
-  for (int i = tid; i < 9 * DCG; i += 256) {
-    const int k = i / DCG, cl = i - k * DCG, c = c0 + cl;
-    const bool ok = c < C;
-    float v = 0.f;
-    switch (k) {
-      case 0: v = ok ? b2.sc[c] : 0.f; break;
-      case 1: v = ok ? b2.sh[c] : 0.f; break;
-      case 2: v = ok ? b2.coef[c] : 0.f; break;
-      case 3: v = ok ? b2.coef[C + c] : 0.f; break;
-      case 4: v = ok ? b2.coef[2 * C + c] : 0.f; break;
-      case 5: v = ok ? bn1.scale[c] : 1.f; break;
-      case 6: v = ok ? bn1.shift[c] : 0.f; break;
-      case 7: v = ok ? bn1.mean[c] : 0.f; break;
-      default: v = ok ? bn1.invstd[c] : 1.f; break;
-    }
-    cst[k][cl] = v;
-  }
+  dw1_fill_wts<K>(wts, w, c0, C);
+  dw1_fill_bwd_cst(cst, b2, bn1, c0, C);
   const int tpf = tiles_x * tiles_y;
   const int tstep = gridDim.x / groups;
   const int fstride = g.H * g.W * C;  // elements per frame (< 2^31: checked by the launcher)
@@ -178,15 +159,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && K == 3 && !PF && RB == 1) ?
           float o[8];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const int cq = v8 * 8 + 2 * q;
-            const v2f gtq = lds2(&gbl[fi][0][cq]), bcq = lds2(&gbl[fi][1][cq]);
-            const v2f z = raw8_pair(rz[i], q), y = raw8_pair(r2[i], q);
-            const v2f tz = fma2(y, lds2(&cst[0][cq]), lds2(&cst[1][cq]));
-            const v2f sg = sigmoid2(tz);
-            const v2f ds = sg * fma2(tz, 1.0f - sg, v2f{1.f, 1.f});
-            const v2f g2 = fma2(z, gtq, bcq) * ds;
-            const v2f v = round2(fma2(lds2(&cst[2][cq]), g2, fma2(lds2(&cst[3][cq]), y, lds2(&cst[4][cq]))),
-                                 (T*)nullptr);
+            const v2f v = bn2_bwd_pair<T>(raw8_pair(rz[i], q), raw8_pair(r2[i], q), cst, gbl[fi], v8 * 8 + 2 * q);
             o[2 * q] = v.x;
             o[2 * q + 1] = v.y;
           }
@@ -335,33 +308,33 @@ static int bwd1_launch(hipStream_t s, const DwGeom& g, const T* dZ, const T* Y2,
   if (FR > 1 && (tiles_x != 1 || tiles_y != 1)) { set_error("dw_bwd1: frame stacking needs whole-map tiles", __FILE__, __LINE__); return -1; }
   const int ntiles = cdiv(g.frames, FR) * tiles_x * tiles_y;
   const int groups = cdiv(g.C, DCG);
-  const int64_t per = (int64_t)g.C * K * K;
-  auto kern = dw_bwd1_kernel<T, K, TH, TW, RS, FR, PF, RB>;
-  const int resident = resident_wgs<dw_bwd1_kernel<T, K, TH, TW, RS, FR, PF, RB>, 256>();
-  int64_t rows = std::min<int64_t>(ntiles, std::max(1, resident / groups));
-  rows = std::max<int64_t>(1, std::min<int64_t>(rows, slab_cap / per));
-  rows = std::min<int64_t>(rows, 1024);  // the plan's BN-stat partial rows
-  const int gx = (int)(rows * groups);
   // XCD-aware order where it measured faster (kbench A/B, interleaved: 56x56 -12 %, 14x14 k3 -10 %,
   // 28x28 / 14x14 k5 -2..-4 %); one channel group (112x112 c32) and the stacked 7x7 tiles +4 %
   const int xcd = DFD_DW_XCD >= 0 ? DFD_DW_XCD : (groups > 1 && g.H >= 14);
-  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), 0, s, g, dZ, Y2, b2, w, Y1, bn1, out, stats, slab, ntiles, groups,
-                     tiles_x, tiles_y, xcd);
-  DFD_HIP_CHECK(hipGetLastError());
-  if (stat_rows) *stat_rows = (int)rows;
-  return launch_reduce_slabs(s, slab, (int)rows, per, dW, accumulate);
+  return dw1_launch<dw_bwd1_kernel<T, K, TH, TW, RS, FR, PF, RB>>(s, ntiles, groups, stat_rows, slab, slab_cap,
+                                                                  (int64_t)g.C * K * K, dW, accumulate, g, dZ, Y2, b2,
+                                                                  w, Y1, bn1, out, stats, slab, ntiles, groups, tiles_x,
+                                                                  tiles_y, xcd);
 }
 
-bool dw_bwd1_covers(const DwGeom& g) {
-  if (g.s != 1 || (g.k != 3 && g.k != 5) || g.pad != g.k / 2 || g.Ho != g.H || g.Wo != g.W) return false;
-  if (!dw_bwd1_enabled()) return false;
+// 1: the stride-1 and stride-2 blocks take the kernels with both BN backward passes fused (this file,
+// k_dw_bwd2.hip)
+bool dw_bwd1_enabled() { return dw_bwd_fused_enabled() && tune(TK_DW_BWD1) != 0; }
+
+// tile configuration for a stride-1 layer: 0 none, 1 two stacked 7x7 frames, 2 8x28 tiles (k3),
+// 3 14x14 tiles
+static int dw1_config(const DwGeom& g) {
+  if (g.s != 1 || (g.k != 3 && g.k != 5) || g.pad != g.k / 2 || g.Ho != g.H || g.Wo != g.W) return 0;
   // channel-pair accesses; 32-bit byte offsets within the tile's frames (FR <= 2; fp32 bound for
   // both dtypes) -- checked here so the caller falls back to the split path instead of failing
-  if (g.C % 2 || (int64_t)g.H * g.W * g.C * 8 >= (1ll << 32)) return false;
-  if (g.H == 7 && g.W == 7) return true;  // two stacked frames per tile
-  if (g.k == 3) return (g.H % 8 == 0 && g.W % 28 == 0) || (g.H % 14 == 0 && g.W % 14 == 0);
-  return g.H % 14 == 0 && g.W % 14 == 0;
+  if (g.C % 2 || (int64_t)g.H * g.W * g.C * 8 >= (1ll << 32)) return 0;
+  if (g.H == 7 && g.W == 7) return 1;
+  if (g.k == 3 && g.H % 8 == 0 && g.W % 28 == 0) return 2;
+  if (g.H % 14 == 0 && g.W % 14 == 0) return 3;
+  return 0;
 }
+
+bool dw_bwd1_covers(const DwGeom& g) { return dw1_config(g) != 0 && dw_bwd1_enabled(); }
 
 // 0: launched; 1: shape not covered (use the BN2 apply + launch_dw_bwd path)
 template <typename T>
@@ -371,37 +344,27 @@ int launch_dw_bwd1(hipStream_t s, const DwGeom& g, const T* dZ, const T* Y2, con
                    bool accumulate) {
   if (!dw_bwd1_covers(g)) return 1;
   const Dw1Bn2 b2{gate, bc, sc2, sh2, coef2};
-  const int H = g.H, W = g.W;
   // bf16: the software-pipelined form (knob dw_pf, default on: kbench dw_bwd1 over the 12 stride-1
   // layers 1,377-1,380 -> 1,350-1,357 us, round 4) where its registers fit the launch bounds;
   // two-row strips (knob dw_rb bit 1, default off: 1,397 us) on the even-height tiles
   const bool pf = sizeof(T) == 2 && tune(TK_DW_PF) != 0;
   const bool rb = sizeof(T) == 2 && (tune(TK_DW_RB) & 2) != 0;
-#define DFD_BWD1_(K_, TH_, TW_, RS_, FR_, RB_, PFOK_)                                                           \
-  return pf && (PFOK_) ? bwd1_launch<T, K_, TH_, TW_, RS_, FR_, sizeof(T) == 2 && (PFOK_), RB_>(                  \
-                             s, g, dZ, Y2, b2, w, Y1, bn1, out, stats, stat_rows, slab, slab_cap, dW, accumulate) \
-                       : bwd1_launch<T, K_, TH_, TW_, RS_, FR_, false, RB_>(s, g, dZ, Y2, b2, w, Y1, bn1, out, stats, \
-                                                                            stat_rows, slab, slab_cap, dW, accumulate)
+#define DFD_BWD1_(K_, TH_, TW_, RS_, FR_, RB_, PFOK_)                                                            \
+  (pf && (PFOK_) ? bwd1_launch<T, K_, TH_, TW_, RS_, FR_, sizeof(T) == 2 && (PFOK_), RB_>(                        \
+                       s, g, dZ, Y2, b2, w, Y1, bn1, out, stats, stat_rows, slab, slab_cap, dW, accumulate)       \
+                 : bwd1_launch<T, K_, TH_, TW_, RS_, FR_, false, RB_>(s, g, dZ, Y2, b2, w, Y1, bn1, out, stats,   \
+                                                                      stat_rows, slab, slab_cap, dW, accumulate))
   // (bf16 only; k5 two-row strips leave no registers for the prefetch)
-#define DFD_BWD1(K_, TH_, TW_, RS_, FR_)                                                                 \
-  do {                                                                                                   \
-    if (rb && (TH_) % 2 == 0)                                                                            \
-      DFD_BWD1_(K_, TH_, TW_, RS_, FR_, ((TH_) % 2 == 0 && sizeof(T) == 2 ? 2 : 1), (K_) == 3);         \
-    DFD_BWD1_(K_, TH_, TW_, RS_, FR_, 1, true);                                                          \
-  } while (0)
-  if (H == 7 && W == 7) {
-    if (g.k == 3) DFD_BWD1(3, 7, 7, 7, 2);
-    DFD_BWD1(5, 7, 7, 7, 2);
+#define DFD_BWD1(K_, TH_, TW_, RS_, FR_)                                                                        \
+  (rb && (TH_) % 2 == 0 ? DFD_BWD1_(K_, TH_, TW_, RS_, FR_, ((TH_) % 2 == 0 && sizeof(T) == 2 ? 2 : 1), (K_) == 3) \
+                        : DFD_BWD1_(K_, TH_, TW_, RS_, FR_, 1, true))
+  switch (dw1_config(g)) {
+    case 1: return g.k == 3 ? DFD_BWD1(3, 7, 7, 7, 2) : DFD_BWD1(5, 7, 7, 7, 2);
+    case 2: return DFD_BWD1(3, 8, 28, 7, 1);
+    default: return g.k == 3 ? DFD_BWD1(3, 14, 14, 7, 1) : DFD_BWD1(5, 14, 14, 7, 1);
   }
-  if (g.k == 3) {
-    if (H % 8 == 0 && W % 28 == 0) DFD_BWD1(3, 8, 28, 7, 1);
-    if (H % 14 == 0 && W % 14 == 0) DFD_BWD1(3, 14, 14, 7, 1);
-    return 1;
-  }
-  if (H % 14 == 0 && W % 14 == 0) DFD_BWD1(5, 14, 14, 7, 1);
 #undef DFD_BWD1_
 #undef DFD_BWD1
-  return 1;
 }
 
 template int launch_dw_bwd1<float>(hipStream_t, const DwGeom&, const float*, const float*, const float*, const float*,

@@ -58,27 +58,8 @@ __global__ __launch_bounds__(256, 2) void dw_bwd2_kernel(
   const int bid = xcd ? xcd_swizzle((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
   const int grp = bid % groups;
   const int c0 = grp * DCG, C = g.C;
-  for (int i = tid; i < K * K * DCG; i += 256) {
-    const int tap = i / DCG, cl = i - tap * DCG;
-    wts[i] = (c0 + cl < C) ? w[(int64_t)(c0 + cl) * K * K + tap] : 0.f;
-  }
-  for (int i = tid; i < 9 * DCG; i += 256) {
-    const int k = i / DCG, cl = i - k * DCG, c = c0 + cl;
-    const bool ok = c < C;
-    float v = 0.f;
-    switch (k) {
-      case 0: v = ok ? b2.sc[c] : 0.f; break;
-      case 1: v = ok ? b2.sh[c] : 0.f; break;
-      case 2: v = ok ? b2.coef[c] : 0.f; break;
-      case 3: v = ok ? b2.coef[C + c] : 0.f; break;
-      case 4: v = ok ? b2.coef[2 * C + c] : 0.f; break;
-      case 5: v = ok ? bn1.scale[c] : 1.f; break;
-      case 6: v = ok ? bn1.shift[c] : 0.f; break;
-      case 7: v = ok ? bn1.mean[c] : 0.f; break;
-      default: v = ok ? bn1.invstd[c] : 1.f; break;
-    }
-    cst[k][cl] = v;
-  }
+  dw1_fill_wts<K>(wts, w, c0, C);
+  dw1_fill_bwd_cst(cst, b2, bn1, c0, C);
   const int tpf = tiles_x * tiles_y;
   const int tstep = gridDim.x / groups;
   const int istride = g.H * g.W * C, ostride = g.Ho * g.Wo * C;
@@ -96,8 +77,8 @@ __global__ __launch_bounds__(256, 2) void dw_bwd2_kernel(
   v2f ss = {0.f, 0.f}, sq = {0.f, 0.f};
 
   for (int t = bid / groups; t < ntiles; t += tstep) {
-    const int f = (t / tpf) * FR, r = t - (t / tpf) * tpf, ty = r / tiles_x;  // first frame of the tile
-    const int iy0 = ty * TH, ix0 = (r - ty * tiles_x) * TW;  // input tile origin (even)
+    const Dw1Tile tl = dw1_tile(t, tpf, tiles_x, FR, TH, TW);
+    const int f = tl.f, iy0 = tl.iy0, ix0 = tl.ix0;          // first frame; input tile origin (even)
     const int ob = iy0 / 2 - 1, oxb = ix0 / 2 - 1;             // staged dY window origin
     // staging in chunks of at most CH 8-channel loads per tensor in flight (the stacked-frame tiles
     // would otherwise hold 2 x 6 raw vectors next to the launch-long dW accumulators)
@@ -136,14 +117,7 @@ __global__ __launch_bounds__(256, 2) void dw_bwd2_kernel(
             const int fi = FR > 1 ? pixl / D::NG1 : 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              const int cq = v8 * 8 + 2 * q;
-              const v2f z = raw8_pair(rz[u], q), y = raw8_pair(r2[u], q);
-              const v2f tz = fma2(y, lds2(&cst[0][cq]), lds2(&cst[1][cq]));
-              const v2f sg = sigmoid2(tz);
-              const v2f ds = sg * fma2(tz, 1.0f - sg, v2f{1.f, 1.f});
-              const v2f g2 = fma2(z, lds2(&gbl[fi][0][cq]), lds2(&gbl[fi][1][cq])) * ds;
-              const v2f v = round2(fma2(lds2(&cst[2][cq]), g2, fma2(lds2(&cst[3][cq]), y, lds2(&cst[4][cq]))),
-                                   (T*)nullptr);
+              const v2f v = bn2_bwd_pair<T>(raw8_pair(rz[u], q), raw8_pair(r2[u], q), cst, gbl[fi], v8 * 8 + 2 * q);
               o[2 * q] = v.x;
               o[2 * q + 1] = v.y;
             }
@@ -279,19 +253,12 @@ static int bwd2_launch(hipStream_t s, const DwGeom& g, const T* dZ, const T* Y2,
   const int tiles_x = g.W / TW, tiles_y = g.H / TH;
   const int ntiles = cdiv(g.frames, FR) * tiles_x * tiles_y;
   const int groups = cdiv(g.C, DCG);
-  const int64_t per = (int64_t)g.C * K * K;
-  const int resident = resident_wgs<dw_bwd2_kernel<T, K, TH, TW, RS, FR>, 256>();
-  int64_t rows = std::min<int64_t>(ntiles, std::max(1, resident / groups));
-  rows = std::max<int64_t>(1, std::min<int64_t>(rows, slab_cap / per));
-  rows = std::min<int64_t>(rows, 1024);
   // XCD-aware order: faster on every stride-2 layer (kbench A/B, interleaved: blocks.1.0 -3 %,
   // 2.0 -11 %, 3.0 -20 %, 5.0 -3 %)
   const int xcd = DFD_DW_XCD >= 0 ? DFD_DW_XCD : (groups > 1);
-  hipLaunchKernelGGL((dw_bwd2_kernel<T, K, TH, TW, RS, FR>), dim3((unsigned)(rows * groups)), dim3(256), 0, s, g, dZ,
-                     Y2, b2, w, Y1, bn1, out, stats, slab, ntiles, groups, tiles_x, tiles_y, xcd);
-  DFD_HIP_CHECK(hipGetLastError());
-  if (stat_rows) *stat_rows = (int)rows;
-  return launch_reduce_slabs(s, slab, (int)rows, per, dW, accumulate);
+  return dw1_launch<dw_bwd2_kernel<T, K, TH, TW, RS, FR>>(s, ntiles, groups, stat_rows, slab, slab_cap,
+                                                          (int64_t)g.C * K * K, dW, accumulate, g, dZ, Y2, b2, w, Y1,
+                                                          bn1, out, stats, slab, ntiles, groups, tiles_x, tiles_y, xcd);
 }
 
 // tile configuration for a stride-2 layer: 0 none, 1 8x56 tiles, 2 whole 28x28 frames (k3),
@@ -316,20 +283,14 @@ int launch_dw_bwd2(hipStream_t s, const DwGeom& g, const T* dZ, const T* Y2, con
                    bool accumulate) {
   if (!dw_bwd2_covers(g)) return 1;
   const Dw1Bn2 b2{gate, bc, sc2, sh2, coef2};
+#define DFD_BWD2(K_, TH_, TW_, RS_, FR_) \
+  bwd2_launch<T, K_, TH_, TW_, RS_, FR_>(s, g, dZ, Y2, b2, w, Y1, bn1, out, stats, stat_rows, slab, slab_cap, dW, accumulate)
   switch (dw2_config(g)) {
-    case 1:
-      if (g.k == 3)
-        return bwd2_launch<T, 3, 8, 56, 14, 1>(s, g, dZ, Y2, b2, w, Y1, bn1, out, stats, stat_rows, slab, slab_cap, dW,
-                                               accumulate);
-      return bwd2_launch<T, 5, 8, 56, 14, 1>(s, g, dZ, Y2, b2, w, Y1, bn1, out, stats, stat_rows, slab, slab_cap, dW,
-                                             accumulate);
-    case 2:
-      return bwd2_launch<T, 3, 28, 28, 14, 1>(s, g, dZ, Y2, b2, w, Y1, bn1, out, stats, stat_rows, slab, slab_cap, dW,
-                                              accumulate);
-    default:
-      return bwd2_launch<T, 5, 14, 14, 14, 4>(s, g, dZ, Y2, b2, w, Y1, bn1, out, stats, stat_rows, slab, slab_cap, dW,
-                                              accumulate);
+    case 1: return g.k == 3 ? DFD_BWD2(3, 8, 56, 14, 1) : DFD_BWD2(5, 8, 56, 14, 1);
+    case 2: return DFD_BWD2(3, 28, 28, 14, 1);
+    default: return DFD_BWD2(5, 14, 14, 14, 4);
   }
+#undef DFD_BWD2
 }
 
 template int launch_dw_bwd2<float>(hipStream_t, const DwGeom&, const float*, const float*, const float*, const float*,

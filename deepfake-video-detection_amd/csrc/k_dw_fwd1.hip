@@ -57,10 +57,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && S == 1) ? 3 : 2) void dw_fw
   const int bid = xcd ? xcd_swizzle((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
   const int grp = bid % groups;
   const int c0 = grp * DCG, C = g.C;
-  for (int i = tid; i < K * K * DCG; i += 256) {
-    const int tap = i / DCG, cl = i - tap * DCG;
-    wts[i] = (c0 + cl < C) ? w[(int64_t)(c0 + cl) * K * K + tap] : 0.f;
-  }
+  dw1_fill_wts<K>(wts, w, c0, C);
   // BN1 scale / shift: finalized here from the producer's stat rows (bnfin.h; the first workgroup of
   // the channel group stores them and the running statistics), or read from the finalize launch's output
   const int nc = C - c0 < DCG ? C - c0 : DCG;
@@ -83,8 +80,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && S == 1) ? 3 : 2) void dw_fw
 
   // raw loads of a tile's staged window (one 8-channel vector per lane and pass)
   auto stage_load = [&](int t, Raw8<T> (&ry)[D::NLD]) {
-    const int f = (t / tpf) * FR, r = t - (t / tpf) * tpf, ty = r / tiles_x;
-    const int iy0 = ty * TH, ix0 = (r - ty * tiles_x) * TW;
+    const Dw1Tile tl = dw1_tile(t, tpf, tiles_x, FR, TH, TW);
+    const int f = tl.f, iy0 = tl.iy0, ix0 = tl.ix0;
     const T* yf = Y1 + (int64_t)f * fstride;
 #pragma unroll
     for (int i = 0; i < D::NLD; ++i) {
@@ -108,8 +105,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && S == 1) ? 3 : 2) void dw_fw
   Raw8<T> ry[D::NLD];
   if (DFD_FWD1_PF && bid / groups < ntiles) stage_load(bid / groups, ry);
   for (int t = bid / groups; t < ntiles; t += tstep) {
-    const int f = (t / tpf) * FR, r = t - (t / tpf) * tpf, ty = r / tiles_x;
-    const int iy0 = ty * TH, ix0 = (r - ty * tiles_x) * TW;
+    const Dw1Tile tl = dw1_tile(t, tpf, tiles_x, FR, TH, TW);
+    const int f = tl.f, iy0 = tl.iy0, ix0 = tl.ix0;
     if (!DFD_FWD1_PF) stage_load(t, ry);
     lds_barrier();  // the previous tile's strips are done with acts
 #pragma unroll
@@ -258,18 +255,16 @@ static int fwd1_launch(hipStream_t s, const DwGeom& g, const T* X, const float* 
   if (FR > 1 && (tiles_x != 1 || tiles_y != 1)) { set_error("dw_fwd1: frame stacking needs whole-map tiles", __FILE__, __LINE__); return -1; }
   const int ntiles = cdiv(g.frames, FR) * tiles_x * tiles_y;
   const int groups = cdiv(g.C, DCG);
-  const int resident = resident_wgs<dw_fwd1_kernel<T, K, TH, TW, RS, FR, S, RB>, 256>();
-  int64_t rows = std::min<int64_t>(ntiles, std::max(1, resident / groups));
-  rows = std::min<int64_t>(rows, 1024);  // the plan's BN-stat partial rows
   // XCD-aware order where it measured faster (kbench A/B: 56x56 s1 -16 %, 14x14 c480 -2..-6 %); the
   // 14x14 k5 c672 (+7 %), stacked 7x7 (+7..12 %) and single-group layers keep dispatch order
   const int xcd = DFD_DW_XCD >= 0 ? DFD_DW_XCD : (groups > 1 && (g.Ho >= 28 || (g.Ho == 14 && g.C <= 480)));
-  hipLaunchKernelGGL((dw_fwd1_kernel<T, K, TH, TW, RS, FR, S, RB>), dim3((unsigned)(rows * groups)), dim3(256), 0, s, g, X, w,
-                     pro, Y, stats, ntiles, groups, tiles_x, tiles_y, xcd, fin ? *fin : BnFwdFin{});
-  DFD_HIP_CHECK(hipGetLastError());
-  if (stat_rows) *stat_rows = (int)rows;
-  return 0;
+  return dw1_launch<dw_fwd1_kernel<T, K, TH, TW, RS, FR, S, RB>>(s, ntiles, groups, stat_rows, nullptr, 0, 0, nullptr,
+                                                                 false, g, X, w, pro, Y, stats, ntiles, groups, tiles_x,
+                                                                 tiles_y, xcd, fin ? *fin : BnFwdFin{});
 }
+
+// 1: the stride-1 forward takes dw_fwd1_kernel (channel pairs)
+bool dw_fwd1_enabled() { return tune(TK_DW_FWD1) != 0; }
 
 // 1: launched, 0: shape not covered, -1: error
 template <typename T>

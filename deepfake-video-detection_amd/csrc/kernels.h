@@ -241,7 +241,8 @@ template <typename T>
 int launch_pw_wgrad(hipStream_t s, const T* dY, const T* X, int64_t M, int N, int K, int pro_mode,
                     const Pro& pro, float* slab, int64_t slab_cap, float* dW, bool accumulate);
 
-// ---------------- depthwise convs: k_dw.hip ----------------
+// ---------------- depthwise convs: k_dw_fwd.hip, k_dw_strip.hip, k_dw_dgrad.hip, k_dw_wgrad.hip, k_dw_bwd.hip;
+// channel-pair kernels: k_dw_fwd1.hip, k_dw_bwd1.hip, k_dw_bwd2.hip ----------------
 struct DwGeom {
   int frames, H, W, C, k, s, pad, Ho, Wo;
 };
