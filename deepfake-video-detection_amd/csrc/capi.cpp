@@ -449,6 +449,72 @@ int dfd_collate_frames(void* stream, const uint8_t* src, const int64_t* sel, int
   DFD_GUARD_END
 }
 
+// ---- augmentation / eval resize (k_augment.hip) ----
+static bool aug_shape_ok(int n, int src_h, int src_w, int out_h, int out_w) {
+  const int64_t lim = (int64_t)1 << 31;
+  if (n < 0 || src_h < 1 || src_w < 1 || out_h < 1 || out_w < 1 || (int64_t)src_h * src_w * 3 >= lim ||
+      (int64_t)std::max(out_h, 8) * std::max(out_w, 8) * 3 >= lim) {
+    dfd::set_error("augment_frames: bad shape", __FILE__, __LINE__);
+    return false;
+  }
+  if (n > 65535) { dfd::set_error("augment_frames: at most 65535 frames per call", __FILE__, __LINE__); return false; }
+  return true;
+}
+
+// the rules of include/dfd_hip.h on one call's tables; nothing is enqueued for a table that fails them
+static bool aug_table_ok(const int32_t* pi, const float* pf, int n, int src_h, int src_w, int out_h, int out_w) {
+  char msg[160];
+  for (int f = 0; f < n; ++f) {
+    const int32_t* r = pi + (int64_t)f * DFD_AUG_PI;
+    const float* q = pf + (int64_t)f * DFD_AUG_PF;
+    const char* bad = nullptr;
+    const int all = DFD_AUG_FLIP | DFD_AUG_JITTER | DFD_AUG_GRAY | DFD_AUG_DOWNUP | DFD_AUG_BLUR;
+    int seen = 0;
+    for (int o = 0; o < 4; ++o)
+      if (r[5 + o] >= 0 && r[5 + o] < 4) seen |= 1 << r[5 + o];
+    if (r[0] & ~all) bad = "unknown flag";
+    else if (r[1] < 0 || r[2] < 0 || r[3] < 1 || r[4] < 1 || (int64_t)r[1] + r[3] > src_h || (int64_t)r[2] + r[4] > src_w)
+      bad = "crop box outside the source";
+    else if (seen != 15) bad = "jitter order is not a permutation of 0..3";
+    else if (r[9] < 0 || r[9] > 255) bad = "hue shift outside 0..255";
+    else if (r[10] < 1 || r[11] < 1 || r[10] > std::max(out_h, 8) || r[11] > std::max(out_w, 8))
+      bad = "downscale size outside 1..max(out, 8)";
+    else if ((r[0] & DFD_AUG_BLUR) && (out_h < 2 || out_w < 2)) bad = "blur needs an output of at least 2 x 2";
+    else
+      for (int k = 0; k < DFD_AUG_PF; ++k)
+        if (!std::isfinite(q[k])) bad = "non-finite factor";
+    if (bad) {
+      snprintf(msg, sizeof(msg), "augment_frames: frame %d: %s", f, bad);
+      dfd::set_error(msg, __FILE__, __LINE__);
+      return false;
+    }
+  }
+  return true;
+}
+
+int64_t dfd_augment_scratch_bytes(int n, int src_h, int src_w, int out_h, int out_w) {
+  if (!aug_shape_ok(n, src_h, src_w, out_h, out_w)) return -1;
+  return dfd::augment_scratch_bytes(n, src_h, src_w, out_h, out_w);
+}
+
+int dfd_augment_lds_resident(int src_h, int src_w, int out_h, int out_w) {
+  if (!aug_shape_ok(1, src_h, src_w, out_h, out_w)) return -1;
+  return dfd::augment_path(src_h, src_w, out_h, out_w);
+}
+
+int dfd_augment_frames(void* stream, const uint8_t* src, int n, int src_h, int src_w, const int32_t* params_i32,
+                       const float* params_f32, int out_h, int out_w, uint8_t* out, void* scratch,
+                       int64_t scratch_bytes) {
+  DFD_GUARD_BEGIN
+  if (!aug_shape_ok(n, src_h, src_w, out_h, out_w)) return -1;
+  if (n == 0) return 0;
+  if (!src || !params_i32 || !params_f32 || !out || !scratch) { dfd::set_error("null argument", __FILE__, __LINE__); return -1; }
+  if (!aug_table_ok(params_i32, params_f32, n, src_h, src_w, out_h, out_w)) return -1;
+  return dfd::launch_augment_frames((hipStream_t)stream, src, n, src_h, src_w, params_i32, params_f32, out_h, out_w,
+                                    out, scratch, scratch_bytes);
+  DFD_GUARD_END
+}
+
 // ---- ResNet-50 ensemble member (inference; k_resnet.hip + hipBLASLt) ----
 int dfd_rn_im2col(void* stream, int dtype, const void* x, int N, int H, int W, int C, int kh, int kw, int stride,
                   int pad, int Kp, void* out) {

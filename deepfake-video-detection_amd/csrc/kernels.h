@@ -494,6 +494,14 @@ int launch_stem_wgrad(hipStream_t s, const StemGeom& g, const void* x, const T* 
 int launch_collate_gather(hipStream_t s, const uint8_t* src, const int64_t* sel, int64_t nsel, int64_t frame_bytes,
                           bool f32, void* out);
 
+// ---------------- augmentation / resize of uint8 face crops: k_augment.hip ----------------
+// The parameter tables (include/dfd_hip.h) are host pointers, already validated by the caller.
+int64_t augment_scratch_bytes(int n, int src_h, int src_w, int out_h, int out_w);
+int augment_path(int src_h, int src_w, int out_h, int out_w);  // 1: LDS-resident working image
+int launch_augment_frames(hipStream_t s, const uint8_t* src, int n, int src_h, int src_w, const int32_t* params_i,
+                          const float* params_f, int out_h, int out_w, uint8_t* out, void* scratch,
+                          int64_t scratch_bytes);
+
 // ---------------- focal / label-smoothed classification losses: k_loss.hip ----------------
 // FocalLoss and nn.CrossEntropyLoss(weight, label_smoothing) of src/train_improved.py:29-78,136-150.
 // q_on = 1 - eps; q_off = eps / (C - 1) (focal; 0 if C == 1) or eps / C (ce).  work: loss_work_floats(B, C)

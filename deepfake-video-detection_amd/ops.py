@@ -14,6 +14,7 @@ implementation for shape propagation, and autograd where the op is differentiabl
   dfd::grad_norm_scaled, dfd::adam_step_scaled,    the same under dynamic loss scaling (fp16 training:
   dfd::loss_scale_update                           GradScaler unscale_ / step / update, on the device)
   dfd::collate_frames                              the collate gather + /255 (train.py:38-61)
+  dfd::augment_frames                              VideoFacesDataset's train / eval transforms (dataset.py:125-142)
 
 Every operator runs on the caller's current HIP stream and raises ``RuntimeError`` (``DFDError``) on
 failure: there is no CPU implementation and no fallback.  The trunk operators take the plan as an
@@ -325,7 +326,51 @@ def _(src, sel, frame_shape, to_float):
     return src.new_empty((sel.numel(), *frame_shape), dtype=torch.float32 if to_float else torch.uint8)
 
 
+# ---------------------------------------------------------------- augmentation / eval resize
+AUG_PI, AUG_PF = 12, 6  # columns of the two parameter tables (include/dfd_hip.h: DFD_AUG_PI / DFD_AUG_PF)
+
+
+def _augment_check(src: Tensor, params_i: Tensor, params_f: Tensor, out_size: List[int]) -> Tuple[int, int, int, int, int]:
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+        raise _lib.DFDError(f"augment_frames: frames must be uint8 (N, H, W, 3), got {src.dtype} {tuple(src.shape)}")
+    n, h, w = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    if len(out_size) != 2:
+        raise _lib.DFDError("augment_frames: out_size is (height, width)")
+    if (params_i.dtype != torch.int32 or tuple(params_i.shape) != (n, AUG_PI) or params_f.dtype != torch.float32
+            or tuple(params_f.shape) != (n, AUG_PF)):
+        raise _lib.DFDError(f"augment_frames: parameter tables must be int32 ({n}, {AUG_PI}) and float32 "
+                            f"({n}, {AUG_PF}), got {params_i.dtype} {tuple(params_i.shape)} and {params_f.dtype} "
+                            f"{tuple(params_f.shape)}")
+    return n, h, w, int(out_size[0]), int(out_size[1])
+
+
+@torch.library.custom_op("dfd::augment_frames", mutates_args=(), device_types="cuda")
+def augment_frames(src: Tensor, params_i: Tensor, params_f: Tensor, out_size: List[int]) -> Tensor:
+    """src uint8 (N,H,W,3), contiguous, on the device; the parameter tables of ``augment.draw_augment_params``
+    (host tensors; device tensors are copied back first) -> uint8 (N, out_h, out_w, 3)."""
+    lib = _lib.load()
+    n, h, w, oh, ow = _augment_check(src, params_i, params_f, out_size)
+    if not src.is_contiguous():
+        raise _lib.DFDError("augment_frames: frames must be contiguous NHWC")
+    pi, pf = params_i.cpu().contiguous(), params_f.cpu().contiguous()
+    nbytes = int(lib.dfd_augment_scratch_bytes(n, h, w, oh, ow))
+    if nbytes < 0:
+        _lib.check(-1)
+    out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=src.device)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=src.device)
+    _lib.check(lib.dfd_augment_frames(_lib.stream_of(src.device), src.data_ptr(), n, h, w, pi.data_ptr(),
+                                      pf.data_ptr(), oh, ow, out.data_ptr(), scratch.data_ptr(), nbytes))
+    return out
+
+
+@augment_frames.register_fake
+def _(src, params_i, params_f, out_size):
+    return src.new_empty((src.shape[0], out_size[0], out_size[1], 3), dtype=torch.uint8)
+
+
 OPS = ("b0_trunk_forward", "b0_trunk_backward", "weighted_cross_entropy", "weighted_cross_entropy_backward",
        "grad_norm", "adam_step", "grad_norm_scaled", "adam_step_scaled", "loss_scale_update", "collate_frames")
 # the losses of the ViT+GCN trainer (losses.FocalLoss / SmoothedCrossEntropyLoss)
 LOSS_OPS = ("classification_loss", "classification_loss_backward")
+# the train / eval transforms in front of the models (augment.TrainAugment / resize_frames)
+AUGMENT_OPS = ("augment_frames",)

@@ -260,6 +260,31 @@ DFD_API int dfd_loss_backward(void* stream, int mode, int reduction, const int64
 DFD_API int dfd_collate_frames(void* stream, const uint8_t* src, const int64_t* sel, int64_t nsel,
                                int64_t frame_bytes, int out_f32, void* out);
 
+/* Train-time augmentation / eval resize of uint8 NHWC face crops (VideoFacesDataset's transforms,
+ * src/dataset.py:125-142, without the JPEG recompression): a deterministic function of the frame
+ * and its row of the two parameter tables, which the HOST draws (deepfake_amd/augment.py).
+ *   params_i32 [n][DFD_AUG_PI]: flags (DFD_AUG_*), crop box top, left, height, width, the four
+ *     colour-jitter operations in application order (0 brightness, 1 contrast, 2 saturation, 3 hue),
+ *     the hue shift in H code values (0..255), and the (h2, w2) of the downscale/upscale stage;
+ *   params_f32 [n][DFD_AUG_PF]: brightness, contrast, saturation factors and the three blur taps.
+ * src (n, src_h, src_w, 3), out (n, out_h, out_w, 3) and scratch are device pointers; the two tables
+ * are HOST pointers: they are validated here (box inside the source, 1 <= h2 <= max(out_h, 8) and the
+ * same for w2, the permutation a permutation, finite factors, blur only on frames of at least 2 x 2,
+ * n <= 65535) and a bad table returns -1 before anything is enqueued.  One kernel launch per call. */
+#define DFD_AUG_PI 12
+#define DFD_AUG_PF 6
+#define DFD_AUG_FLIP 1
+#define DFD_AUG_JITTER 2
+#define DFD_AUG_GRAY 4
+#define DFD_AUG_DOWNUP 8
+#define DFD_AUG_BLUR 16
+DFD_API int64_t dfd_augment_scratch_bytes(int n, int src_h, int src_w, int out_h, int out_w);
+/* 1: the working image of this shape stays in LDS; 0: it goes through the scratch; -1: bad shape */
+DFD_API int dfd_augment_lds_resident(int src_h, int src_w, int out_h, int out_w);
+DFD_API int dfd_augment_frames(void* stream, const uint8_t* src, int n, int src_h, int src_w,
+                               const int32_t* params_i32, const float* params_f32, int out_h, int out_w,
+                               uint8_t* out, void* scratch, int64_t scratch_bytes);
+
 /* ---- ResNet-50 ensemble member, inference (src/pretrained_detector.py:37-40 -> torchvision
  * resnet50 children[:-1]; EnsembleDetector default ENSEMBLE_BACKBONES, app.py:661,1597).  NHWC
  * activations, dtype 0 = fp32, 1 = bf16.  Every convolution is dfd_rn_conv, an implicit-GEMM MFMA
