@@ -90,6 +90,8 @@ _SIGS = {
     "dfd_augment_scratch_bytes": (c_i64, [c_i, c_i, c_i, c_i, c_i]),
     "dfd_augment_lds_resident": (c_i, [c_i, c_i, c_i, c_i]),
     "dfd_augment_frames": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_i64]),
+    "dfd_augment_jpeg_scratch_bytes": (c_i64, [c_i, c_i, c_i, c_i, c_i]),
+    "dfd_augment_frames_jpeg": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i64]),
     "dfd_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_d, c_d, c_i, c_d, c_i, c_p]),
     "dfd_grad_norm_scaled": (c_i, [c_p, c_p, c_i64, c_f, c_p, c_p, c_p]),
     "dfd_adam_step_scaled": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_d, c_d, c_d, c_d, c_d, c_d, c_i, c_p, c_p]),

@@ -11,9 +11,13 @@ that ``pipeline.collate_clips(out="uint8")`` already keeps on the device
 restates Pillow's arithmetic (the backend torchvision documents for PIL inputs) and is held to Pillow's
 results by ``tests/test_augment_*.py``.
 
-NOT covered: the JPEG recompression (``_RandomJPEGCompression``).  A libjpeg-exact codec is a piece of
-work of its own; the parameter tables reserve no field for it and ``draw_augment_params`` draws nothing
-for it.  A trainer that needs it has to run it on the host.
+The JPEG recompression (``_RandomJPEGCompression``: ``save(format='JPEG', quality=q, optimize=True)`` and
+``open().convert('RGB')``, p 0.5, q 35-95) is a stage of the same launch, between the downscale/upscale and the
+blur (``torch.ops.dfd.augment_frames_jpeg`` -> ``dfd_augment_frames_jpeg``): libjpeg-turbo's baseline 4:2:0 round
+trip restated in 32-bit integers, byte for byte what Pillow returns (``tests/golden/augment_jpeg.npz``).  Its
+quality travels beside the tables as an int32 ``(N,)`` array (0: stage off for that frame), drawn by
+``draw_jpeg_quality``.  It is opt-in, ``TrainAugment(..., jpeg=True)``: the default chain and the draws of
+``draw_augment_params`` are what they were before the stage existed.
 
 Parameter tables (``include/dfd_hip.h``), one row per frame:
 
@@ -74,8 +78,8 @@ def draw_augment_params(n: int, src_hw, out_hw, generator: torch.Generator | Non
     the four operations, factors uniform in ``[max(0, 1 - v), 1 + v]``, hue uniform in ``[-hue, hue]``),
     ``_RandomDownscaleUpscale`` (``max(8, int(dim * s))``) and ``GaussianBlur`` (sigma uniform).  The
     STREAM of draws is this project's own (37 uniforms per frame from ``generator``): a seed does not
-    reproduce what torchvision and ``random`` would have drawn from theirs.  Nothing is drawn for the JPEG
-    recompression, which the device chain leaves out."""
+    reproduce what torchvision and ``random`` would have drawn from theirs.  Nothing is drawn here for the JPEG
+    recompression: ``draw_jpeg_quality`` draws for it, from the same generator, after this function."""
     h, w = int(src_hw[0]), int(src_hw[1])
     oh, ow = int(out_hw[0]), int(out_hw[1])
     u = torch.rand(n, _DRAWS, dtype=torch.float64, generator=generator).numpy()
@@ -126,10 +130,26 @@ def draw_augment_params(n: int, src_hw, out_hw, generator: torch.Generator | Non
     return torch.from_numpy(pi), torch.from_numpy(pf)
 
 
-def augment_frames(frames: torch.Tensor, params_i: torch.Tensor, params_f: torch.Tensor, out_size) -> torch.Tensor:
-    """uint8 (N,H,W,3) on the device + the two tables -> uint8 (N, out_h, out_w, 3); one HIP launch."""
+def draw_jpeg_quality(n: int, generator: torch.Generator | None = None, p=0.5, quality=(35, 95)) -> torch.Tensor:
+    """Draw the JPEG quality of ``n`` frames -> int32 ``(N,)`` CPU tensor: 0 (the frame skips the stage) or the
+    quality.  ``_RandomJPEGCompression`` (``dataset.py:83-105``): applied when ``u0 < p`` (the reference skips on
+    ``random.random() > p``), at ``random.randint(lo, hi)``, both ends inclusive.  Two uniforms per frame from
+    ``generator``, the project's own stream as in ``draw_augment_params``."""
+    lo, hi = int(quality[0]), int(quality[1])
+    u = torch.rand(n, 2, dtype=torch.float64, generator=generator).numpy()
+    q = np.minimum(lo + np.floor(u[:, 1] * (hi - lo + 1)).astype(np.int64), hi)
+    return torch.from_numpy(np.where(u[:, 0] < p, q, 0).astype(np.int32))
+
+
+def augment_frames(frames: torch.Tensor, params_i: torch.Tensor, params_f: torch.Tensor, out_size,
+                   quality: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8 (N,H,W,3) on the device + the two tables -> uint8 (N, out_h, out_w, 3); one HIP launch.  With
+    ``quality`` (int32 ``(N,)`` CPU tensor, 0 or 1..100 per frame) the launch includes the JPEG recompression."""
     _lib.require_hip(frames, "frames")
-    return torch.ops.dfd.augment_frames(frames, params_i, params_f, [int(out_size[0]), int(out_size[1])])
+    size = [int(out_size[0]), int(out_size[1])]
+    if quality is None:
+        return torch.ops.dfd.augment_frames(frames, params_i, params_f, size)
+    return torch.ops.dfd.augment_frames_jpeg(frames, params_i, params_f, quality, size)
 
 
 def resize_frames(frames: torch.Tensor, out_size) -> torch.Tensor:
@@ -142,11 +162,18 @@ def resize_frames(frames: torch.Tensor, out_size) -> torch.Tensor:
 class TrainAugment:
     """The train transform on a ``(B,T,3,H,W)`` uint8 batch as ``collate_clips(out="uint8")`` returns it:
     views the batch back to NHWC, draws one row per frame, launches, and returns ``(B,T,3,h,w)`` uint8 in
-    the same channels-last layout."""
+    the same channels-last layout.
 
-    def __init__(self, image_size=(224, 224), generator: torch.Generator | None = None, **draw_kwargs):
+    The JPEG recompression is opt-in: with ``jpeg=True`` a quality per frame is drawn (``draw_jpeg_quality`` with
+    ``jpeg_p``, ``jpeg_quality``) after the tables, on the same generator, and the stage runs in the same launch.
+    The reference's full train recipe is ``TrainAugment(image_size, generator, jpeg=True)``; the default leaves
+    the stage out and draws exactly what it drew before the stage existed."""
+
+    def __init__(self, image_size=(224, 224), generator: torch.Generator | None = None, *, jpeg=False, jpeg_p=0.5,
+                 jpeg_quality=(35, 95), **draw_kwargs):
         self.image_size = (int(image_size[0]), int(image_size[1]))
         self.generator = generator
+        self.jpeg, self.jpeg_p, self.jpeg_quality = bool(jpeg), float(jpeg_p), (int(jpeg_quality[0]), int(jpeg_quality[1]))
         self.draw_kwargs = draw_kwargs
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
@@ -155,5 +182,6 @@ class TrainAugment:
         b, t, _, h, w = x.shape
         frames = x.permute(0, 1, 3, 4, 2).contiguous().view(b * t, h, w, 3)  # no copy for collate_clips' layout
         pi, pf = draw_augment_params(b * t, (h, w), self.image_size, self.generator, **self.draw_kwargs)
-        out = augment_frames(frames, pi, pf, self.image_size)
+        q = draw_jpeg_quality(b * t, self.generator, self.jpeg_p, self.jpeg_quality) if self.jpeg else None
+        out = augment_frames(frames, pi, pf, self.image_size, q)
         return out.view(b, t, *self.image_size, 3).permute(0, 1, 4, 2, 3)

@@ -494,7 +494,12 @@ static bool aug_table_ok(const int32_t* pi, const float* pf, int n, int src_h, i
 
 int64_t dfd_augment_scratch_bytes(int n, int src_h, int src_w, int out_h, int out_w) {
   if (!aug_shape_ok(n, src_h, src_w, out_h, out_w)) return -1;
-  return dfd::augment_scratch_bytes(n, src_h, src_w, out_h, out_w);
+  return dfd::augment_scratch_bytes(n, src_h, src_w, out_h, out_w, false);
+}
+
+int64_t dfd_augment_jpeg_scratch_bytes(int n, int src_h, int src_w, int out_h, int out_w) {
+  if (!aug_shape_ok(n, src_h, src_w, out_h, out_w)) return -1;
+  return dfd::augment_scratch_bytes(n, src_h, src_w, out_h, out_w, true);
 }
 
 int dfd_augment_lds_resident(int src_h, int src_w, int out_h, int out_w) {
@@ -510,8 +515,31 @@ int dfd_augment_frames(void* stream, const uint8_t* src, int n, int src_h, int s
   if (n == 0) return 0;
   if (!src || !params_i32 || !params_f32 || !out || !scratch) { dfd::set_error("null argument", __FILE__, __LINE__); return -1; }
   if (!aug_table_ok(params_i32, params_f32, n, src_h, src_w, out_h, out_w)) return -1;
-  return dfd::launch_augment_frames((hipStream_t)stream, src, n, src_h, src_w, params_i32, params_f32, out_h, out_w,
-                                    out, scratch, scratch_bytes);
+  return dfd::launch_augment_frames((hipStream_t)stream, src, n, src_h, src_w, params_i32, params_f32, nullptr, out_h,
+                                    out_w, out, scratch, scratch_bytes);
+  DFD_GUARD_END
+}
+
+int dfd_augment_frames_jpeg(void* stream, const uint8_t* src, int n, int src_h, int src_w, const int32_t* params_i32,
+                            const float* params_f32, const int32_t* quality, int out_h, int out_w, uint8_t* out,
+                            void* scratch, int64_t scratch_bytes) {
+  DFD_GUARD_BEGIN
+  if (!aug_shape_ok(n, src_h, src_w, out_h, out_w)) return -1;
+  if (n == 0) return 0;
+  if (!src || !params_i32 || !params_f32 || !quality || !out || !scratch) {
+    dfd::set_error("null argument", __FILE__, __LINE__);
+    return -1;
+  }
+  if (!aug_table_ok(params_i32, params_f32, n, src_h, src_w, out_h, out_w)) return -1;
+  for (int f = 0; f < n; ++f)
+    if (quality[f] < 0 || quality[f] > 100) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "augment_frames: frame %d: JPEG quality %d outside 0..100", f, (int)quality[f]);
+      dfd::set_error(msg, __FILE__, __LINE__);
+      return -1;
+    }
+  return dfd::launch_augment_frames((hipStream_t)stream, src, n, src_h, src_w, params_i32, params_f32, quality, out_h,
+                                    out_w, out, scratch, scratch_bytes);
   DFD_GUARD_END
 }
 

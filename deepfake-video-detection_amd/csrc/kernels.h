@@ -496,11 +496,13 @@ int launch_collate_gather(hipStream_t s, const uint8_t* src, const int64_t* sel,
 
 // ---------------- augmentation / resize of uint8 face crops: k_augment.hip ----------------
 // The parameter tables (include/dfd_hip.h) are host pointers, already validated by the caller.
-int64_t augment_scratch_bytes(int n, int src_h, int src_w, int out_h, int out_w);
+// quality: nullptr (the chain without the JPEG stage, scratch of jpeg = false) or n host values in 0..100 (0: stage
+// off for that frame; scratch of jpeg = true).
+int64_t augment_scratch_bytes(int n, int src_h, int src_w, int out_h, int out_w, bool jpeg);
 int augment_path(int src_h, int src_w, int out_h, int out_w);  // 1: LDS-resident working image
 int launch_augment_frames(hipStream_t s, const uint8_t* src, int n, int src_h, int src_w, const int32_t* params_i,
-                          const float* params_f, int out_h, int out_w, uint8_t* out, void* scratch,
-                          int64_t scratch_bytes);
+                          const float* params_f, const int32_t* quality, int out_h, int out_w, uint8_t* out,
+                          void* scratch, int64_t scratch_bytes);
 
 // ---------------- focal / label-smoothed classification losses: k_loss.hip ----------------
 // FocalLoss and nn.CrossEntropyLoss(weight, label_smoothing) of src/train_improved.py:29-78,136-150.

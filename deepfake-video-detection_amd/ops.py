@@ -15,6 +15,7 @@ implementation for shape propagation, and autograd where the op is differentiabl
   dfd::loss_scale_update                           GradScaler unscale_ / step / update, on the device)
   dfd::collate_frames                              the collate gather + /255 (train.py:38-61)
   dfd::augment_frames                              VideoFacesDataset's train / eval transforms (dataset.py:125-142)
+  dfd::augment_frames_jpeg                         the same with the JPEG recompression stage (dataset.py:83-105)
 
 Every operator runs on the caller's current HIP stream and raises ``RuntimeError`` (``DFDError``) on
 failure: there is no CPU implementation and no fallback.  The trunk operators take the plan as an
@@ -368,9 +369,37 @@ def _(src, params_i, params_f, out_size):
     return src.new_empty((src.shape[0], out_size[0], out_size[1], 3), dtype=torch.uint8)
 
 
+@torch.library.custom_op("dfd::augment_frames_jpeg", mutates_args=(), device_types="cuda")
+def augment_frames_jpeg(src: Tensor, params_i: Tensor, params_f: Tensor, quality: Tensor, out_size: List[int]) -> Tensor:
+    """``augment_frames`` with the JPEG recompression between the downscale/upscale and the blur, in the same launch.
+    quality: int32 (N,) host tensor of ``augment.draw_jpeg_quality``, 0 (stage off for that frame) or 1..100."""
+    lib = _lib.load()
+    n, h, w, oh, ow = _augment_check(src, params_i, params_f, out_size)
+    if quality.dtype != torch.int32 or tuple(quality.shape) != (n,) or quality.device.type != "cpu":
+        raise _lib.DFDError(f"augment_frames: quality must be an int32 ({n},) CPU tensor, got {quality.dtype} "
+                            f"{tuple(quality.shape)} on {quality.device}")
+    if not src.is_contiguous():
+        raise _lib.DFDError("augment_frames: frames must be contiguous NHWC")
+    pi, pf, q = params_i.cpu().contiguous(), params_f.cpu().contiguous(), quality.contiguous()
+    nbytes = int(lib.dfd_augment_jpeg_scratch_bytes(n, h, w, oh, ow))
+    if nbytes < 0:
+        _lib.check(-1)
+    out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=src.device)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=src.device)
+    _lib.check(lib.dfd_augment_frames_jpeg(_lib.stream_of(src.device), src.data_ptr(), n, h, w, pi.data_ptr(),
+                                           pf.data_ptr(), q.data_ptr(), oh, ow, out.data_ptr(), scratch.data_ptr(),
+                                           nbytes))
+    return out
+
+
+@augment_frames_jpeg.register_fake
+def _(src, params_i, params_f, quality, out_size):
+    return src.new_empty((src.shape[0], out_size[0], out_size[1], 3), dtype=torch.uint8)
+
+
 OPS = ("b0_trunk_forward", "b0_trunk_backward", "weighted_cross_entropy", "weighted_cross_entropy_backward",
        "grad_norm", "adam_step", "grad_norm_scaled", "adam_step_scaled", "loss_scale_update", "collate_frames")
 # the losses of the ViT+GCN trainer (losses.FocalLoss / SmoothedCrossEntropyLoss)
 LOSS_OPS = ("classification_loss", "classification_loss_backward")
 # the train / eval transforms in front of the models (augment.TrainAugment / resize_frames)
-AUGMENT_OPS = ("augment_frames",)
+AUGMENT_OPS = ("augment_frames", "augment_frames_jpeg")

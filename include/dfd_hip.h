@@ -261,8 +261,9 @@ DFD_API int dfd_collate_frames(void* stream, const uint8_t* src, const int64_t* 
                                int64_t frame_bytes, int out_f32, void* out);
 
 /* Train-time augmentation / eval resize of uint8 NHWC face crops (VideoFacesDataset's transforms,
- * src/dataset.py:125-142, without the JPEG recompression): a deterministic function of the frame
- * and its row of the two parameter tables, which the HOST draws (deepfake_amd/augment.py).
+ * src/dataset.py:125-142): a deterministic function of the frame and its row of the two parameter
+ * tables, which the HOST draws (deepfake_amd/augment.py).  The JPEG recompression of the train chain
+ * is dfd_augment_frames_jpeg below.
  *   params_i32 [n][DFD_AUG_PI]: flags (DFD_AUG_*), crop box top, left, height, width, the four
  *     colour-jitter operations in application order (0 brightness, 1 contrast, 2 saturation, 3 hue),
  *     the hue shift in H code values (0..255), and the (h2, w2) of the downscale/upscale stage;
@@ -284,6 +285,17 @@ DFD_API int dfd_augment_lds_resident(int src_h, int src_w, int out_h, int out_w)
 DFD_API int dfd_augment_frames(void* stream, const uint8_t* src, int n, int src_h, int src_w,
                                const int32_t* params_i32, const float* params_f32, int out_h, int out_w,
                                uint8_t* out, void* scratch, int64_t scratch_bytes);
+/* The same chain with the reference's JPEG recompression (_RandomJPEGCompression, src/dataset.py:83-105)
+ * between the downscale/upscale and the blur, in the same single launch: quality[n] (HOST pointer) holds
+ * 0 (stage off for that frame) or the quality 1..100; a frame with a quality comes out byte for byte as
+ * Pillow's save(format='JPEG', quality=q, optimize=True) + open().convert('RGB') (libjpeg-turbo, baseline,
+ * 4:2:0) returns it.  The tables follow dfd_augment_frames' rules (flag bits above DFD_AUG_BLUR stay
+ * unknown: the quality is no flag); a quality outside 0..100 returns -1 before anything is enqueued.
+ * The scratch also holds the qualities: size it with dfd_augment_jpeg_scratch_bytes. */
+DFD_API int64_t dfd_augment_jpeg_scratch_bytes(int n, int src_h, int src_w, int out_h, int out_w);
+DFD_API int dfd_augment_frames_jpeg(void* stream, const uint8_t* src, int n, int src_h, int src_w,
+                                    const int32_t* params_i32, const float* params_f32, const int32_t* quality,
+                                    int out_h, int out_w, uint8_t* out, void* scratch, int64_t scratch_bytes);
 
 /* ---- ResNet-50 ensemble member, inference (src/pretrained_detector.py:37-40 -> torchvision
  * resnet50 children[:-1]; EnsembleDetector default ENSEMBLE_BACKBONES, app.py:661,1597).  NHWC
