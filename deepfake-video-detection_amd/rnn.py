@@ -61,6 +61,9 @@ class LogicRNNLSTM(FlatModule):
 
     def forward(self, x: torch.Tensor, lengths: torch.Tensor | None = None) -> torch.Tensor:
         self.ensure_flat()
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("gradient w.r.t. the input features is not provided by the HIP LogicRNNLSTM: "
+                                      "detach them, or run the trunk that produced them under no_grad")
         _lib.require_hip(x, "x")
         if x.dim() != 3 or x.shape[2] != self.input_size:
             raise ValueError(f"expected (B, T, {self.input_size}), got {tuple(x.shape)}")
