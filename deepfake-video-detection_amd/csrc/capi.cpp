@@ -374,6 +374,20 @@ int dfd_loss_backward(void* stream, int mode, int reduction, const int64_t* labe
   DFD_GUARD_END
 }
 
+int dfd_metrics_append(void* stream, const float* logits, const int64_t* labels, const float* loss, int B,
+                       int64_t offset, int64_t capacity, float* probs, uint8_t* tags, double* loss_sums) {
+  DFD_GUARD_BEGIN
+  return dfd::metrics_append((hipStream_t)stream, logits, labels, loss, B, offset, capacity, probs, tags, loss_sums);
+  DFD_GUARD_END
+}
+
+int dfd_metrics_finalize(void* stream, const float* probs, const uint8_t* tags, int64_t N, const float* thresholds,
+                         int n_thresholds, int64_t* result) {
+  DFD_GUARD_BEGIN
+  return dfd::metrics_finalize((hipStream_t)stream, probs, tags, N, thresholds, n_thresholds, result);
+  DFD_GUARD_END
+}
+
 int dfd_grad_norm(void* stream, const float* grads, int64_t n, float max_norm, void* scratch, float* out2) {
   DFD_GUARD_BEGIN
   return dfd::grad_norm((hipStream_t)stream, grads, n, max_norm, (double*)scratch, 1024, out2);

@@ -523,6 +523,18 @@ int loss_forward(hipStream_t s, const LossDesc& d, const float* z, const int64_t
 int loss_backward(hipStream_t s, const LossDesc& d, const int64_t* y, const float* w, const float* work,
                   const float* gout, float* dz);
 
+// ---------------- device-side epoch metrics (binary, 2 logits): k_metrics.hip ----------------
+// The per-epoch bookkeeping of EnsembleTrainer.train_epoch / validate (src/ensemble_trainer.py:203-211,266-329)
+// without a per-step host read.  probs (capacity) fp32, tags (capacity) bytes, loss_sums 2 doubles {sum loss,
+// sum loss * B}; loss: a device scalar or null.  thresholds: HOST floats (passed to the kernel by value).
+// result: kMetricsResultWords int64, layout at the top of k_metrics.hip.  Both launchers only enqueue.
+constexpr int kMetricsMaxThresholds = 32;
+constexpr int kMetricsResultWords = 72;
+int metrics_append(hipStream_t s, const float* logits, const int64_t* labels, const float* loss, int B, int64_t offset,
+                   int64_t capacity, float* probs, uint8_t* tags, double* loss_sums);
+int metrics_finalize(hipStream_t s, const float* probs, const uint8_t* tags, int64_t N, const float* thresholds,
+                     int n_thresholds, int64_t* result);
+
 // ---------------- misc: k_misc.hip ----------------
 struct CastSeg {
   int64_t src, dst;  // element offsets

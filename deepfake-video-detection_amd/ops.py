@@ -10,6 +10,9 @@ implementation for shape propagation, and autograd where the op is differentiabl
   dfd::weighted_cross_entropy (+ _backward)        nn.CrossEntropyLoss(weight) (ensemble_trainer.py:358)
   dfd::classification_loss (+ _backward)           FocalLoss / nn.CrossEntropyLoss(weight, label_smoothing)
                                                    (train_improved.py:29-78, 136-150)
+  dfd::metrics_append, dfd::metrics_finalize       the per-step bookkeeping and the per-epoch reductions behind the
+                                                   metrics of train_epoch / validate (ensemble_trainer.py:203-211,
+                                                   266-329), kept on the device: one host read per epoch
   dfd::grad_norm, dfd::adam_step                   clip_grad_norm_(1.0) + AdamW (ensemble_trainer.py:196-200)
   dfd::grad_norm_scaled, dfd::adam_step_scaled,    the same under dynamic loss scaling (fp16 training:
   dfd::loss_scale_update                           GradScaler unscale_ / step / update, on the device)
@@ -227,6 +230,59 @@ def _loss_backward(ctx, gloss, _gwork):
 classification_loss.register_autograd(_loss_backward, setup_context=_loss_setup)
 
 
+# ---------------------------------------------------------------- device-side epoch metrics
+METRICS_MAX_THRESHOLDS = 32
+METRICS_RESULT_WORDS = 72  # include/dfd_hip.h: DFD_METRICS_RESULT_WORDS, layout at dfd_metrics_finalize
+
+
+# probs / tags / loss_sums: the epoch's state (metrics.EpochMetrics owns it); rows offset .. offset + B - 1 are written
+@torch.library.custom_op("dfd::metrics_append", mutates_args=("probs", "tags", "loss_sums"), device_types="cuda")
+def metrics_append(logits: Tensor, labels: Tensor, loss: Optional[Tensor], offset: int, probs: Tensor, tags: Tensor,
+                   loss_sums: Tensor) -> None:
+    """logits (B, 2), labels (B) int64, loss a device scalar or None -> probs[offset + r] = softmax(logits[r])[1],
+    tags[offset + r] = label | prediction << 1 | labelled << 2, loss_sums += (loss, loss * B).  No host sync."""
+    if logits.dim() != 2 or logits.shape[1] != 2 or labels.shape != logits.shape[:1]:
+        raise _lib.DFDError(f"metrics_append: needs (B, 2) logits and (B) labels, got {tuple(logits.shape)} and "
+                            f"{tuple(labels.shape)}")
+    if (probs.dtype != torch.float32 or tags.dtype != torch.uint8 or loss_sums.dtype != torch.float64
+            or tags.numel() != probs.numel() or loss_sums.numel() != 2
+            or not (probs.is_contiguous() and tags.is_contiguous() and loss_sums.is_contiguous())):
+        raise _lib.DFDError("metrics_append: state must be fp32 probs, uint8 tags of the same length and 2 fp64 sums")
+    logits = logits.contiguous().float()
+    labels = labels.contiguous().long()
+    loss = None if loss is None else loss.reshape(1).float()
+    _lib.check(_lib.load().dfd_metrics_append(_lib.stream_of(logits.device), logits.data_ptr(), labels.data_ptr(),
+                                              _lib.ptr(loss), logits.shape[0], int(offset), probs.numel(),
+                                              probs.data_ptr(), tags.data_ptr(), loss_sums.data_ptr()))
+
+
+@metrics_append.register_fake
+def _(logits, labels, loss, offset, probs, tags, loss_sums):
+    return None
+
+
+@torch.library.custom_op("dfd::metrics_finalize", mutates_args=(), device_types="cuda")
+def metrics_finalize(probs: Tensor, tags: Tensor, n: int, thresholds: List[float]) -> Tensor:
+    """-> the int64 result block of the first n rows (counts, confusion counts, U2, per-threshold tp / fp; layout in
+    include/dfd_hip.h).  thresholds: at most 32 values, rounded to fp32 here.  Enqueues only."""
+    import ctypes
+
+    if probs.dtype != torch.float32 or tags.dtype != torch.uint8 or not 0 <= n <= min(probs.numel(), tags.numel()):
+        raise _lib.DFDError("metrics_finalize: needs fp32 probs, uint8 tags and 0 <= n <= their length")
+    if len(thresholds) > METRICS_MAX_THRESHOLDS:
+        raise _lib.DFDError(f"metrics_finalize: at most {METRICS_MAX_THRESHOLDS} thresholds (got {len(thresholds)})")
+    thr = (ctypes.c_float * max(len(thresholds), 1))(*[float(t) for t in thresholds])
+    out = torch.empty(METRICS_RESULT_WORDS, dtype=torch.int64, device=probs.device)
+    _lib.check(_lib.load().dfd_metrics_finalize(_lib.stream_of(probs.device), probs.data_ptr(), tags.data_ptr(),
+                                                int(n), thr, len(thresholds), out.data_ptr()))
+    return out
+
+
+@metrics_finalize.register_fake
+def _(probs, tags, n, thresholds):
+    return probs.new_empty(METRICS_RESULT_WORDS, dtype=torch.int64)
+
+
 # ---------------------------------------------------------------- optimizer
 # scratch: the kernel's fixed-order partial sums (written); out: [norm, clip coefficient]
 @torch.library.custom_op("dfd::grad_norm", mutates_args=("scratch", "out"), device_types="cuda")
@@ -401,5 +457,7 @@ OPS = ("b0_trunk_forward", "b0_trunk_backward", "weighted_cross_entropy", "weigh
        "grad_norm", "adam_step", "grad_norm_scaled", "adam_step_scaled", "loss_scale_update", "collate_frames")
 # the losses of the ViT+GCN trainer (losses.FocalLoss / SmoothedCrossEntropyLoss)
 LOSS_OPS = ("classification_loss", "classification_loss_backward")
+# the epoch accumulator of metrics.EpochMetrics / trainer.EnsembleTrainer
+METRICS_OPS = ("metrics_append", "metrics_finalize")
 # the train / eval transforms in front of the models (augment.TrainAugment / resize_frames)
 AUGMENT_OPS = ("augment_frames", "augment_frames_jpeg")

@@ -252,6 +252,32 @@ DFD_API int dfd_loss_backward(void* stream, int mode, int reduction, const int64
                               int B, int C, double gamma, double label_smoothing, int64_t ignore_index,
                               const float* work, const float* grad_out, float* dlogits);
 
+/* ---- device-side epoch metrics ------------------------------------------------------------
+ * Replaces the per-step bookkeeping of EnsembleTrainer.train_epoch / validate (src/ensemble_trainer.py:
+ * 203-211, 266-273: loss.item() and three .cpu() copies per step) and the reductions behind its metrics
+ * (:276-329) for a binary classifier with 2 logits.  The caller owns the state: probs (capacity floats),
+ * tags (capacity bytes), loss_sums (2 doubles: sum of loss, sum of loss * B), all device memory, and
+ * counts the rows it has appended itself.  Neither call allocates, synchronises or copies.
+ * dfd_metrics_append: rows offset .. offset + B - 1 get softmax(logits)[1] (fp32) and a tag byte
+ * (DFD_METRICS_TAG_*: label, argmax prediction with ties to class 0, labelled); a label other than 0 / 1
+ * (-1: unlabelled) is stored and skipped by the finalize.  loss: a device scalar added to loss_sums in
+ * stream order, or NULL.  -1 for B <= 0, offset < 0, offset + B > capacity, a null pointer.
+ * dfd_metrics_finalize: zeroes result (DFD_METRICS_RESULT_WORDS int64) on the stream and fills it from the
+ * first N rows: [0] n_pos [1] n_neg [2] tn [3] fp [4] fn [5] tp [6] U2 = sum over (i positive, j negative)
+ * of 2 [p_i > p_j] + [p_i == p_j] (AUC = U2 / (2 n_pos n_neg)) [8 + t] / [40 + t] true / false positives
+ * of `prob >= thresholds[t]` in fp32.  thresholds: n_thresholds <= 32 HOST floats.  Integer reductions
+ * only: the same bits on every run.  -1 for N < 0, more than 32 thresholds, a null pointer; N == 0 is
+ * valid (all zero). */
+#define DFD_METRICS_TAG_LABEL 1
+#define DFD_METRICS_TAG_PRED 2
+#define DFD_METRICS_TAG_VALID 4
+#define DFD_METRICS_MAX_THRESHOLDS 32
+#define DFD_METRICS_RESULT_WORDS 72
+DFD_API int dfd_metrics_append(void* stream, const float* logits, const int64_t* labels, const float* loss, int B,
+                               int64_t offset, int64_t capacity, float* probs, uint8_t* tags, double* loss_sums);
+DFD_API int dfd_metrics_finalize(void* stream, const float* probs, const uint8_t* tags, int64_t N,
+                                 const float* thresholds, int n_thresholds, int64_t* result);
+
 /* ---- input pipeline ----------------------------------------------------------------------
  * Replaces the frame gather of collate_batch_cnn_lstm / collate_batch (src/train.py:38-61,
  * 62-100): out[s] = src[sel[s]] for s < nsel, frames of frame_bytes uint8 each (sel[s] < 0: an
