@@ -87,6 +87,8 @@ _SIGS = {
     "dfd_loss_backward": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_d, c_d, c_i64, c_p, c_p, c_p]),
     "dfd_metrics_append": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i64, c_i64, c_p, c_p, c_p]),
     "dfd_metrics_finalize": (c_i, [c_p, c_p, c_p, c_i64, ctypes.POINTER(c_f), c_i, c_p]),
+    "dfd_ensemble_decide_floats": (c_i64, [c_i]),
+    "dfd_ensemble_decide": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p]),
     "dfd_grad_norm": (c_i, [c_p, c_p, c_i64, c_f, c_p, c_p]),
     "dfd_collate_frames": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_i, c_p]),
     "dfd_augment_scratch_bytes": (c_i64, [c_i, c_i, c_i, c_i, c_i]),

@@ -12,6 +12,8 @@ the app (training resume, the serving service below, tests):
 * ``safe_load_state_dict``     -- load only shape-matching keys, ``strict=False`` (``:1476-1488``)
 * ``load_pretrained``          -- the ``'pretrained'`` branch of ``load_model``: backbone inference,
   stats, safe load, the ``match_ratio < 0.80`` refusal (``:1681-1749``)
+* ``load_ensemble``            -- the ``'ensemble_pretrained'`` branch: member count from the keys, the app's
+  candidate backbone lists scored by key compatibility, ``ensemble_method='weighted'`` (``:1593-1679``)
 
 and the trainers' save formats: a raw ``state_dict`` (``EnsembleTrainer._save_checkpoint``,
 ``src/ensemble_trainer.py:549-571``) and ``{'epoch', 'model_state', 'optimizer_state',
@@ -224,6 +226,130 @@ def load_pretrained(path_or_obj, device=None, compute_dtype="fp32", checkpoint_n
     stats["missing"] = len(getattr(inc, "missing_keys", []) or [])
     stats["unexpected"] = len(getattr(inc, "unexpected_keys", []) or [])
     stats = {**stats, **base, "backbone": backbone, "backbones": None,
+             "fake_class_index_detected": int(fake_idx) if fake_idx is not None else None}
+    mr = stats.get("match_ratio")
+    if mr is not None and float(mr) < 0.80:
+        raise IncompatibleCheckpoint(f"Incompatible checkpoint (match_ratio={mr:.3f}).")
+    if device is not None:
+        model = model.to(device)
+    return model.eval(), stats
+
+
+# ------------------------------------------------------------------ ensembles (app.py:1593-1679)
+DEFAULT_ENSEMBLE_BACKBONES = ("efficientnet_b0", "resnet50")
+ENSEMBLE_POOL = ("efficientnet_b0", "resnet50", "resnet34", "resnet18", "vit_base_patch16_224")
+ENSEMBLE_PRESETS = {
+    1: [[x] for x in ENSEMBLE_POOL],
+    2: [["efficientnet_b0", "resnet50"], ["efficientnet_b0", "resnet34"], ["efficientnet_b0", "resnet18"],
+        ["resnet34", "resnet50"], ["resnet18", "resnet50"], ["efficientnet_b0", "vit_base_patch16_224"]],
+    3: [["efficientnet_b0", "resnet50", "resnet34"], ["efficientnet_b0", "resnet50", "resnet18"],
+        ["efficientnet_b0", "resnet34", "resnet18"], ["efficientnet_b0", "resnet50", "vit_base_patch16_224"]],
+}
+
+
+def infer_ensemble_count(sd):
+    """Number of members from the ``models.<i>.`` keys, or None (app.py:1434-1447)."""
+    try:
+        idxs = set()
+        for k in sd.keys():
+            if isinstance(k, str) and k.startswith("models."):
+                parts = k.split(".")
+                if len(parts) >= 2 and parts[1].isdigit():
+                    idxs.add(int(parts[1]))
+        return max(idxs) + 1 if idxs else None
+    except Exception:
+        return None
+
+
+def is_ensemble_state_dict(sd):
+    return isinstance(sd, dict) and infer_ensemble_count(sd) is not None
+
+
+def compat_score(model, sd):
+    """(matched, -mismatched, -missing, -unexpected): higher is better (app.py:1449-1474)."""
+    try:
+        msd = model.state_dict()
+    except Exception:
+        return (0, -10**9, -10**9, -10**9)
+    matched = mismatched = 0
+    for k, v in sd.items():
+        if k in msd:
+            if _shape_ok(msd, k, v):
+                matched += 1
+            else:
+                mismatched += 1
+    return (matched, -mismatched, -len([k for k in msd if k not in sd]), -len([k for k in sd if k not in msd]))
+
+
+def ensemble_candidates(requested, n_models):
+    """The backbone lists the app tries for an ``n_models``-member checkpoint, in its order (app.py:1604-1644)."""
+    requested, n_models = list(requested), int(n_models)
+    if n_models in ENSEMBLE_PRESETS:
+        candidates = [list(c) for c in ENSEMBLE_PRESETS[n_models]]
+    else:  # the requested list, truncated or padded from the pool
+        bb = list(requested)
+        if len(bb) >= n_models:
+            candidates = [bb[:n_models]]
+        else:
+            for x in ENSEMBLE_POOL:
+                if len(bb) >= n_models:
+                    break
+                if x not in bb:
+                    bb.append(x)
+            candidates = [bb]
+    if requested not in candidates and len(requested) == n_models:
+        candidates.insert(0, requested)
+    return candidates
+
+
+def load_ensemble(path_or_obj, device=None, compute_dtype="fp32", meta=None):
+    """``load_model(path, 'ensemble_pretrained')`` for the HIP ensemble (app.py:1593-1679, 1714-1758): returns
+    ``(model, stats)`` with an ``EnsembleDetector(..., ensemble_method='weighted')`` in eval mode on ``device``.
+
+    The requested backbones are ``meta['backbones']``, else ``ENSEMBLE_BACKBONES``, else the default pair; the member
+    count comes from the checkpoint's ``models.<i>.`` keys and the app's candidate lists of that length are scored by
+    key compatibility (the first best wins).  A candidate naming a backbone without a HIP trunk is skipped, as a
+    candidate whose constructor fails is in the app.  Raises ``IncompatibleCheckpoint`` where the app returns False
+    (no state dict, ``match_ratio < 0.80``) and where no supported candidate has the checkpoint's member count."""
+    import os
+
+    from .pretrained_detector import EnsembleDetector
+
+    ckpt = read_checkpoint(path_or_obj)
+    sd = extract_state_dict(ckpt)
+    fake_idx = detect_fake_class_index(ckpt)
+    if not (isinstance(sd, dict) and sd):
+        raise IncompatibleCheckpoint("No state_dict found")
+    sd = normalize_state_dict_keys(sd)
+    backbones = (meta or {}).get("backbones")
+    if not isinstance(backbones, (list, tuple)) or not backbones:
+        env = os.environ.get("ENSEMBLE_BACKBONES", ",".join(DEFAULT_ENSEMBLE_BACKBONES))
+        backbones = [x.strip() for x in str(env).split(",") if x.strip()]
+    requested = list(backbones)
+    n_models = infer_ensemble_count(sd) or len(requested)
+
+    def build(names):
+        return EnsembleDetector(backbone_names=list(names), pretrained=False, num_classes=2, dropout_rate=0.5,
+                                ensemble_method="weighted", compute_dtype=compute_dtype)
+
+    best = None  # (names, score, model)
+    for cand in ensemble_candidates(requested, n_models):
+        if len(cand) != n_models or any(b not in SUPPORTED_BACKBONES for b in cand):
+            continue
+        model = build(cand)
+        score = compat_score(model, sd)
+        if best is None or score > best[1]:
+            best = (list(cand), score, model)
+    if best is None:
+        raise IncompatibleCheckpoint(
+            f"No supported ensemble of {n_models} member(s) for this checkpoint (requested {requested}; the MI355X "
+            f"path implements {', '.join(SUPPORTED_BACKBONES)})")
+    chosen, _, model = best
+    stats = load_stats(model, sd)
+    inc = safe_load_state_dict(model, sd)
+    stats["missing"] = len(getattr(inc, "missing_keys", []) or [])
+    stats["unexpected"] = len(getattr(inc, "unexpected_keys", []) or [])
+    stats = {**stats, "model_type": "ensemble_pretrained", "backbone": None, "backbones": chosen,
              "fake_class_index_detected": int(fake_idx) if fake_idx is not None else None}
     mr = stats.get("match_ratio")
     if mr is not None and float(mr) < 0.80:

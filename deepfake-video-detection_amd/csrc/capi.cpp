@@ -388,6 +388,21 @@ int dfd_metrics_finalize(void* stream, const float* probs, const uint8_t* tags, 
   DFD_GUARD_END
 }
 
+int64_t dfd_ensemble_decide_floats(int M) {
+  DFD_GUARD_BEGIN
+  return dfd::ensemble_decide_floats(M);
+  DFD_GUARD_END
+}
+
+int dfd_ensemble_decide(void* stream, const float* member_logits, const float* member_scores, const float* weights,
+                        int M, int64_t V, int C, int T, int method, int fake_idx, float temperature, float* logits,
+                        float* scores, float* block) {
+  DFD_GUARD_BEGIN
+  return dfd::ensemble_decide((hipStream_t)stream, member_logits, member_scores, weights, M, V, C, T, method, fake_idx,
+                              temperature, logits, scores, block);
+  DFD_GUARD_END
+}
+
 int dfd_grad_norm(void* stream, const float* grads, int64_t n, float max_norm, void* scratch, float* out2) {
   DFD_GUARD_BEGIN
   return dfd::grad_norm((hipStream_t)stream, grads, n, max_norm, (double*)scratch, 1024, out2);

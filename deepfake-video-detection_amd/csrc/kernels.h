@@ -535,6 +535,21 @@ int metrics_append(hipStream_t s, const float* logits, const int64_t* labels, co
 int metrics_finalize(hipStream_t s, const float* probs, const uint8_t* tags, int64_t N, const float* thresholds,
                      int n_thresholds, int64_t* result);
 
+// ---------------- serving an ensemble: k_ensemble.hip ----------------
+// The combination of EnsembleDetector.forward (src/pretrained_detector.py:196-216) and the fp32 values of the app's
+// decision step (app.py:2090-2094, 2130-2143) for V videos in one launch.  member_logits (M, V, 2), member_scores
+// (M, V, T), weights (M) raw (softmax inside) or null; logits (V, 2), scores (V, T), block (V, 5 + 2M): layout at the
+// top of k_ensemble.hip.  Refuses M outside 1..8, C != 2, T outside 1..64, V < 1, an unknown method, fake_idx outside
+// {0, 1}, temperature <= 0, a null pointer, weighted without weights -- before anything is launched.  Enqueues only.
+constexpr int kEnsembleMaxMembers = 8;
+constexpr int kEnsembleMaxFrames = 64;
+constexpr int kEnsembleBlockBase = 5;
+constexpr int kEnsembleAverage = 0, kEnsembleWeighted = 1, kEnsembleVoting = 2;
+int64_t ensemble_decide_floats(int M);
+int ensemble_decide(hipStream_t s, const float* member_logits, const float* member_scores, const float* weights, int M,
+                    int64_t V, int C, int T, int method, int fake_idx, float temperature, float* logits, float* scores,
+                    float* block);
+
 // ---------------- misc: k_misc.hip ----------------
 struct CastSeg {
   int64_t src, dst;  // element offsets

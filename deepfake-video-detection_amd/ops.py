@@ -13,6 +13,9 @@ implementation for shape propagation, and autograd where the op is differentiabl
   dfd::metrics_append, dfd::metrics_finalize       the per-step bookkeeping and the per-epoch reductions behind the
                                                    metrics of train_epoch / validate (ensemble_trainer.py:203-211,
                                                    266-329), kept on the device: one host read per epoch
+  dfd::ensemble_decide                             serving an EnsembleDetector: the combination of the members'
+                                                   outputs (pretrained_detector.py:196-216) and the fp32 values of the
+                                                   app's decision step (app.py:2090-2143) for a batch of videos
   dfd::grad_norm, dfd::adam_step                   clip_grad_norm_(1.0) + AdamW (ensemble_trainer.py:196-200)
   dfd::grad_norm_scaled, dfd::adam_step_scaled,    the same under dynamic loss scaling (fp16 training:
   dfd::loss_scale_update                           GradScaler unscale_ / step / update, on the device)
@@ -283,6 +286,51 @@ def _(probs, tags, n, thresholds):
     return probs.new_empty(METRICS_RESULT_WORDS, dtype=torch.int64)
 
 
+# ---------------------------------------------------------------- serving an ensemble
+ENSEMBLE_METHODS = {"average": 0, "weighted": 1, "voting": 2}  # include/dfd_hip.h: DFD_ENSEMBLE_*
+ENSEMBLE_BLOCK_BASE = 5  # words in front of the 2M per-member probabilities of a decision-block row
+
+
+@torch.library.custom_op("dfd::ensemble_decide", mutates_args=(), device_types="cuda")
+def ensemble_decide(member_logits: Tensor, member_scores: Tensor, weights: Optional[Tensor], method: str, fake_idx: int,
+                    temperature: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """member logits (M, V, 2), member frame scores (M, V, T), the raw ensemble weights (M) or None -> the ensemble's
+    (logits (V, 2), scores (V, T), decision block (V, 5 + 2M)) of EnsembleDetector.forward and the app's decision step,
+    in one launch (layout: include/dfd_hip.h, dfd_ensemble_decide).  Eval only: no autograd.  Enqueues only."""
+    if method not in ENSEMBLE_METHODS:
+        raise _lib.DFDError(f"ensemble_decide: unknown ensemble method {method!r}")
+    if member_logits.dim() != 3 or member_scores.dim() != 3 or member_scores.shape[:2] != member_logits.shape[:2]:
+        raise _lib.DFDError(f"ensemble_decide: needs (M, V, C) logits and (M, V, T) scores, got "
+                            f"{tuple(member_logits.shape)} and {tuple(member_scores.shape)}")
+    M, V, C = (int(d) for d in member_logits.shape)
+    T = int(member_scores.shape[2])
+    if weights is not None and (weights.dim() != 1 or weights.numel() != M):
+        raise _lib.DFDError(f"ensemble_decide: needs {M} ensemble weights, got {tuple(weights.shape)}")
+    zl = member_logits.detach().contiguous().float()
+    zs = member_scores.detach().contiguous().float()
+    w = None if weights is None else weights.detach().contiguous().float()
+    lib = _lib.load()
+    words = int(lib.dfd_ensemble_decide_floats(M))
+    if words < 0:
+        _lib.check(-1)
+    dev = zl.device
+    logits = torch.empty((V, 2), dtype=torch.float32, device=dev)
+    scores = torch.empty((V, T), dtype=torch.float32, device=dev)
+    block = torch.empty((V, words), dtype=torch.float32, device=dev)
+    _lib.check(lib.dfd_ensemble_decide(_lib.stream_of(dev), zl.data_ptr(), zs.data_ptr(), _lib.ptr(w), M, V, C, T,
+                                       ENSEMBLE_METHODS[method], int(fake_idx), float(temperature),
+                                       logits.data_ptr(), scores.data_ptr(), block.data_ptr()))
+    return logits, scores, block
+
+
+@ensemble_decide.register_fake
+def _(member_logits, member_scores, weights, method, fake_idx, temperature):
+    M, V = member_logits.shape[0], member_logits.shape[1]
+    f32 = torch.float32
+    return (member_logits.new_empty((V, 2), dtype=f32), member_logits.new_empty((V, member_scores.shape[2]), dtype=f32),
+            member_logits.new_empty((V, ENSEMBLE_BLOCK_BASE + 2 * M), dtype=f32))
+
+
 # ---------------------------------------------------------------- optimizer
 # scratch: the kernel's fixed-order partial sums (written); out: [norm, clip coefficient]
 @torch.library.custom_op("dfd::grad_norm", mutates_args=("scratch", "out"), device_types="cuda")
@@ -461,3 +509,5 @@ LOSS_OPS = ("classification_loss", "classification_loss_backward")
 METRICS_OPS = ("metrics_append", "metrics_finalize")
 # the train / eval transforms in front of the models (augment.TrainAugment / resize_frames)
 AUGMENT_OPS = ("augment_frames", "augment_frames_jpeg")
+# the ensemble combination and decision block of serving.FrameClassifierService
+SERVING_OPS = ("ensemble_decide",)

@@ -244,3 +244,30 @@ class EnsembleDetector(nn.Module):
             ens = torch.mode(preds, dim=0)[0]
             return F.one_hot(ens, num_classes=2).float(), scores.mean(dim=0)
         raise ValueError(f"Unknown ensemble method: {self.ensemble_method}")
+
+    def forward_members(self, x: torch.Tensor, fake_idx: int = 1, temperature: float = 1.0,
+                        return_block: bool = False):
+        """Serving forward: every member runs ONCE under ``no_grad`` and its outputs are kept, where the app runs
+        ``MODEL(x)`` and then every member again for its own logits (``app.py:2088-2134``).
+
+        Returns ``(ensemble_logits (V, C), ensemble_scores (V, T), member_logits (M, V, C), member_scores
+        (M, V, T))``.  Nothing is combined here: the ensemble's logits and scores come out of ``dfd::ensemble_decide``
+        (one launch), together with the decision block (``include/dfd_hip.h``) for ``fake_idx`` / ``temperature``,
+        which ``return_block=True`` appends as a fifth element.  Eval only: in training mode it raises (the members
+        would draw dropout masks and update BatchNorm statistics; ``forward`` is the training path)."""
+        if self.training:
+            raise RuntimeError("EnsembleDetector.forward_members is the eval-mode serving forward; call .eval() first "
+                               "(forward() is the training path)")
+        if self.ensemble_method not in ("average", "weighted", "voting"):
+            raise ValueError(f"Unknown ensemble method: {self.ensemble_method}")
+        with torch.no_grad():
+            outs = [m(x) for m in self.models]
+            member_logits = torch.stack([o[0] for o in outs], dim=0)
+            member_scores = torch.stack([o[1] for o in outs], dim=0)
+            weights = self.weights if self.ensemble_method == "weighted" else None
+            logits, scores, block = torch.ops.dfd.ensemble_decide(member_logits, member_scores, weights,
+                                                                  self.ensemble_method, int(fake_idx),
+                                                                  float(temperature))
+        if return_block:
+            return logits, scores, member_logits, member_scores, block
+        return logits, scores, member_logits, member_scores

@@ -278,6 +278,31 @@ DFD_API int dfd_metrics_append(void* stream, const float* logits, const int64_t*
 DFD_API int dfd_metrics_finalize(void* stream, const float* probs, const uint8_t* tags, int64_t N,
                                  const float* thresholds, int n_thresholds, int64_t* result);
 
+/* ---- serving an ensemble --------------------------------------------------------------------
+ * The combination of EnsembleDetector.forward (src/pretrained_detector.py:196-216) and the fp32 values of the
+ * app's ensemble decision step (app.py:2090-2094, 2130-2143; the enhanced agent's softmaxes,
+ * src/enhanced_decision_agent.py:115-138) for V videos in ONE launch: every member runs once, the host reads
+ * one block back per batch.  All device memory, fp32, contiguous:
+ *   member_logits (M, V, 2), member_scores (M, V, T), weights (M) the raw ensemble weights (softmax inside) or NULL
+ *   logits (V, 2): average = sum over members / M; weighted = sum of logits * softmax(weights); voting = one-hot of
+ *     the modal argmax (argmax and mode ties -> class 0, as torch.argmax / torch.mode)
+ *   scores (V, T): the weighted sum (weighted) or the mean over members (average, voting)
+ *   block (V, dfd_ensemble_decide_floats(M) = 5 + 2M): [0] softmax(logits)[fake_idx] [1] softmax(logits)[1 - fake_idx]
+ *     [2] softmax(logits / temperature)[fake_idx] [3] modal argmax of the members [4] M
+ *     [5 + m] softmax(member m)[fake_idx] [5 + M + m] softmax(member m / temperature)[fake_idx]
+ * -1, with nothing launched, for M outside 1..DFD_ENSEMBLE_MAX_MEMBERS, C != 2, T outside 1..DFD_ENSEMBLE_MAX_FRAMES,
+ * V < 1, an unknown method, fake_idx outside {0, 1}, temperature <= 0 or not finite, a null pointer, or
+ * DFD_ENSEMBLE_WEIGHTED without weights.  Neither allocates, synchronises nor copies. */
+#define DFD_ENSEMBLE_AVERAGE 0
+#define DFD_ENSEMBLE_WEIGHTED 1
+#define DFD_ENSEMBLE_VOTING 2
+#define DFD_ENSEMBLE_MAX_MEMBERS 8
+#define DFD_ENSEMBLE_MAX_FRAMES 64
+DFD_API int64_t dfd_ensemble_decide_floats(int M);
+DFD_API int dfd_ensemble_decide(void* stream, const float* member_logits, const float* member_scores,
+                                const float* weights, int M, int64_t V, int C, int T, int method, int fake_idx,
+                                float temperature, float* logits, float* scores, float* block);
+
 /* ---- input pipeline ----------------------------------------------------------------------
  * Replaces the frame gather of collate_batch_cnn_lstm / collate_batch (src/train.py:38-61,
  * 62-100): out[s] = src[sel[s]] for s < nsel, frames of frame_bytes uint8 each (sel[s] < 0: an
